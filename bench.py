@@ -1,6 +1,6 @@
 """bench.py -- training rays/s of the LiDAR4D ray-rendering hot path on MI355X (BASELINE.json metric).
 
-    python bench.py [--gpus N --steps K --warmup W] [--workload c3|c2|c5 ...]
+    python bench.py [--gpus N --steps K --warmup W] [--workload c3|c2|c5 ...] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \
         bench.py --gpus N --steps K --warmup W
 
@@ -12,7 +12,7 @@ batch of synthetic KITTI-360-shaped rays (64 x 1024 panorama, T = 768 samples pe
 MSE ray-drop, MSE intensity: runner.py:179-213) + the ray-chamfer term (runner.py:215-220, always on in the reference)
 + the scene-flow consistency loss (runner.py:222-253, ``--flow_loss`` defaults to True there), backward, GradScaler
 check / skip / update, Adam.  The parameter EMA is updated once per epoch (runner.py:534-535).  ``--no-chamfer --no-flow``
-gives the bare three-loss step; the default run also times it and reports it under ``variants``.
+gives the bare three-loss step; a ``--full`` run also times it and reports it under ``variants``.
 Default workload = BASELINE.json configs[2] ("C3": full 4D field, 16,384 rays/batch/GPU), whose 8-GPU weak-scaled form is
 configs[3] (131,072 rays/step), the configuration the headline ">= 10 M training rays/s on 8 x MI355X" is quoted on.
 Rank r draws its own ray indices (all ranks step through the same frame sequence, so that the per-step work is the same
@@ -22,7 +22,16 @@ timed region.
 The ONE stdout line stays under 4 KB (compact_line): the contract's fields plus scalar summaries; everything listed below in
 full goes to the side file bench_detail.json (L4D_BENCH_DETAIL), whose path is the line's ``detail`` field.
 
-Besides the contract's fields the line / the detail record carry (rank 0, N = 1):
+A plain run does what the headline figure needs and nothing else: set-up, the GradScaler settling loop, the warm-up, the
+timed steps, ``--dump-outputs`` if given, the line.  ``--dump-outputs DIR`` writes what the last timed step produced as
+DIR/<name>.npy (float32, 64 MB at most; inputs are seeded, so equal arguments give equal inputs in every run): training
+workloads the step's ``loss`` and the ``params`` it updated in place with the ``grads`` it updated them with (as the arena
+holds them: multiplied by the loss scale) -- every entry of a tensor of up to 65,536 entries, a fixed seeded sample of 65,536
+entries of a larger one (arena_sample_index); the inference workload the frame's ``raydrop``, ``intensity`` and ``depth``.
+Two runs of one build agree to summation order, not bit for bit: the tables' gradients are scattered with float atomics, and
+Adam turns their last-bit differences into parameter differences of up to a few learning-rate steps where a gradient is near zero.
+
+``--full`` adds every other measurement; besides the contract's fields its line / detail record carry (rank 0, N = 1):
   roofline          the dominant single kernel against ITS roof (see ``kernel_models``): HBM-streaming kernels against the
                     8 TB/s HBM peak with their compulsory bytes; gather kernels against the 34.5 TB/s L2 peak with the
                     table-entry bytes the algorithm touches (the tables, 97 MB, sit in L2 / Infinity Cache, so dividing those
@@ -337,7 +346,10 @@ def parse_args():
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--workload", default="c3", choices=sorted(WORKLOADS))
-    ap.add_argument("--no-cpu-baseline", action="store_true", help="skip the CPU baseline and the parity check that uses its reference outputs")
+    ap.add_argument("--full", action="store_true", help="every measurement besides the headline: per-kernel roofline pass, hash encoder alone, "
+                                                        "three-loss and trained-state steps, CPU baseline and oracle parity (a plain run: the headline only)")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="write what the last timed step produced to DIR/<name>.npy (float32, at most 64 MB)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU baseline and the parity check that uses its reference outputs")
     ap.add_argument("--no-chamfer", action="store_true", help="drop the ray chamfer loss term (runner.py:215-220; always on in the reference)")
     ap.add_argument("--no-flow", action="store_true", help="drop the scene-flow consistency loss (runner.py:222-253; the reference's default is on)")
     ap.add_argument("--chamfer", action="store_true", help=argparse.SUPPRESS)  # accepted for older command lines: now the default
@@ -349,16 +361,19 @@ def parse_args():
     ap.add_argument("--graph", action="store_true", help="training workloads: one hipGraph replay per step (Trainer.train_step_graphed) instead of eager launches")
     ap.add_argument("--no-graph", action="store_true", help=argparse.SUPPRESS)  # the default
     ap.add_argument("--settle-max", type=int, default=250, help="upper bound of the loss-scale settling loop before the warm-up (0: none; counter passes of the profiling script)")
-    ap.add_argument("--profile-steps", type=int, default=2, help="steps of the per-kernel timing pass (0: no roofline block)")
-    ap.add_argument("--variant-steps", type=int, default=10, help="timed steps of each secondary measurement (0: skip them)")
-    ap.add_argument("--trained-steps", type=int, default=200, help="further training steps before the trained-state measurement")
+    ap.add_argument("--profile-steps", type=int, default=2, help="--full: steps of the per-kernel timing pass (0: no roofline block)")
+    ap.add_argument("--variant-steps", type=int, default=10, help="--full: timed steps of each secondary measurement (0: skip them)")
+    ap.add_argument("--trained-steps", type=int, default=200, help="--full: further training steps before the trained-state measurement")
     ap.add_argument("--flow-stream", dest="flow_stream", action="store_true", default=None, help="the scene-flow term on a stream of its own next to the render path (Trainer(flow_loss_stream=True))")
     ap.add_argument("--no-flow-stream", dest="flow_stream", action="store_false", help="... on the render path's stream")
     ap.add_argument("--force-dist", action="store_true", help="under torchrun with ONE rank: take the multi-rank code path anyway (RCCL init, barrier, two-phase gradient all-reduce) -- exercises the data-parallel path on a single-GPU box")
     ap.add_argument("--grad-transport", default="fp32", choices=("fp32", "bf16"), help="wire format of the hash-table / plane gradient ranges in the all-reduce (trainer.GradReducer)")
     ap.add_argument("--streams", type=int, default=None, help="l4d_streams_config mask (bit 0: encode in parts, 1: field adjoint forked, 2: static-grid pre-pass next to the LDS kernel); default: the library's")
     ap.add_argument("--no-overlap", action="store_true", help="one all-reduce of the whole gradient arena behind the backward pass instead of two overlapped phases")
-    return ap.parse_args()
+    args = ap.parse_args()
+    if args.dump_outputs and args.steps < 1:
+        ap.error("--dump-outputs needs at least one timed step")
+    return args
 
 
 PLUMBING = os.environ.get("L4D_BENCH_PLUMBING") == "1"  # tests/test_distributed_cpu.py: the launch / rendezvous / reduce / print
@@ -479,6 +494,45 @@ def compact_line(detail, args):
     return line
 
 
+DUMP_LIMIT_BYTES = 64 << 20  # --dump-outputs: all arrays together
+DUMP_PER_TENSOR = 1 << 16    # arena entries kept per parameter tensor
+
+
+def arena_sample_index(store, per_tensor=DUMP_PER_TENSOR, seed=0):
+    """Positions in the flat parameter arena that --dump-outputs writes: every entry of a tensor of at most ``per_tensor``
+    entries; of a larger one, one position in each of ``per_tensor`` equal slices, drawn from a generator seeded with ``seed``
+    -- the same positions in every run, and every tensor represented (the MLPs whole, next to the hash tables and planes)."""
+    g = torch.Generator().manual_seed(seed)
+    parts = []
+    for _, _, off, n, _ in store.entries:
+        if n <= per_tensor:
+            parts.append(torch.arange(off, off + n))
+        else:
+            s = n // per_tensor
+            parts.append(off + torch.arange(per_tensor) * s + torch.randint(0, s, (per_tensor,), generator=g))
+    return torch.cat(parts)
+
+
+def training_outputs(model, loss):
+    """What a caller of the training step receives: the loss it returns and the parameters it updated in place, with the
+    gradients it updated them with (the arena's values: multiplied by the loss scale), at arena_sample_index's positions."""
+    st = model._store
+    idx = arena_sample_index(st).to(st.flat.device)
+    return {"loss": loss.detach().reshape(1), "params": st.flat[idx], "grads": st.flat_grad[idx]}
+
+
+def write_outputs(out_dir, arrays):
+    """--dump-outputs: every array as <out_dir>/<name>.npy in float32."""
+    import numpy as np
+    host = {k: v.detach().float().cpu().numpy() for k, v in arrays.items()}
+    total = sum(a.nbytes for a in host.values())
+    if total > DUMP_LIMIT_BYTES:
+        raise RuntimeError(f"bench.py --dump-outputs: {total} bytes exceed the {DUMP_LIMIT_BYTES}-byte limit")
+    os.makedirs(out_dir, exist_ok=True)
+    for k, a in host.items():
+        np.save(os.path.join(out_dir, k + ".npy"), a)
+
+
 def main():
     args = parse_args()
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
@@ -581,9 +635,10 @@ def _run(args):
         def step():
             fr = frames[counter[0] % len(frames)]
             counter[0] += 1
-            _, _, pred_depth = trainer.test_step(fr, refine=True)
+            pred = trainer.test_step(fr, refine=True)  # (ray-drop, intensity, depth)
             gt = fr["images_lidar"]
-            meter.update(pred_depth, gt[..., 2] * gt[..., 0])
+            meter.update(pred[2], gt[..., 2] * gt[..., 0])
+            return pred
     else:
         step = trainer.train_step
     step_mode = "eager launches"
@@ -667,7 +722,14 @@ def _run(args):
     reducer = getattr(trainer, "reducer", None)
     if reducer is not None:
         reducer.record_timing = True  # two events per step around GradReducer.finish: how much of the all-reduce was NOT hidden
-    dt = timed(step, args.steps, barrier)
+    last = []
+
+    def step_keep():  # --dump-outputs: what the last timed step returned
+        last[:] = [step()]
+    dt = timed(step_keep if args.dump_outputs else step, args.steps, barrier)
+    if args.dump_outputs and rank == 0:
+        write_outputs(args.dump_outputs, dict(zip(("raydrop", "intensity", "depth"), last[0])) if inference
+                      else training_outputs(model, last[0]))
     allreduce = None
     if reducer is not None:
         reducer.record_timing = False
@@ -695,7 +757,8 @@ def _run(args):
 
     # ---- per-kernel timing pass (HIP events around every kernel launch, on the launch stream), outside the timed region ----
     roofline, roofline_kernels, mfma, per_step = None, None, None, {}
-    if args.profile_steps > 0:
+    profile = args.full and args.profile_steps > 0
+    if profile:
         # every rank runs the extra steps (they contain the gradient all-reduce); only rank 0 records events
         # eager launches (a graph replay does not pass the library's launch sites) with the side streams off: every kernel
         # is timed alone on the chip, which is what its roofline fraction refers to
@@ -711,7 +774,7 @@ def _run(args):
         barrier()
         _lib.lib().l4d_streams_config(mask_was)
         trainer.flow_loss_stream = fls_was
-    if rank == 0 and args.profile_steps > 0:
+    if rank == 0 and profile:
         kernels = {}
         for name, ms in _lib.profile_stop():
             kernels.setdefault(name, []).append(ms)
@@ -849,7 +912,7 @@ def _run(args):
 
     # ---- secondary measurements (single GPU): hash encoder alone, three-loss step, trained state ----
     hash_enc, variants = None, None
-    if rank == 0 and world == 1 and not inference and args.variant_steps > 0:
+    if rank == 0 and world == 1 and not inference and args.full and args.variant_steps > 0:
         import numpy as np
         from lidar4d_amd.gridmeta import GridMeta
         b = data.batch_for(25)
@@ -964,7 +1027,7 @@ def _run(args):
         if inference:
             detail["eval"] = {"chamfer_distance_m2, f_score@0.05": [float(v) for v in meter.measure()], "frames": meter.N,
                               "note": "random-init field vs synthetic ground truth: exercises the eval path, not a quality claim"}
-        if world == 1 and not args.no_cpu_baseline and not inference:
+        if world == 1 and args.full and not args.no_cpu_baseline and not inference:
             with tempfile.TemporaryDirectory() as td:
                 ref_path = os.path.join(td, "parity_ref.npz")
                 detail["cpu_baseline"] = cpu_baseline(51, KITTI360_SCALE, ref_path)

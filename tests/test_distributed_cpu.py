@@ -182,3 +182,43 @@ def test_bench_line_is_compact(tmp_path, monkeypatch):
     assert rf["frac"] == detail["roofline"]["frac"] and rf["traffic"] > 0 and 0 < rf["l2_miss_rate"] < 1
     assert back["cpu_baseline"]["kind"] == "port" and back["cpu_baseline"]["cores"] == 32
     assert json.load(open(tmp_path / "bench_detail.json"))["roofline_kernels"] == detail["roofline_kernels"]
+
+
+def test_bench_dump_outputs_sample(tmp_path):
+    """bench.py --dump-outputs on the benchmark's default model (built on the host: the sampling and the files need no GPU):
+    the same arena positions in every run, every parameter tensor represented (small ones whole), params / grads / loss
+    written as float32 .npy files that load back unchanged, within the 64 MB limit, and a dump over the limit refused."""
+    import importlib.util
+    import os
+    import numpy as np
+    import pytest
+    import torch
+    from lidar4d_amd import LiDAR4D
+    from lidar4d_amd.data import KITTI360_SCALE
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    spec = importlib.util.spec_from_file_location("bench_under_test", os.path.join(root, "bench.py"))
+    bench = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(bench)
+    torch.manual_seed(0)
+    model = LiDAR4D(near_lidar=1.0 * KITTI360_SCALE, far_lidar=81.0 * KITTI360_SCALE, num_frames=51)
+    st = model._store
+    st.prepare_grads()
+    st.flat_grad.normal_()
+    idx = bench.arena_sample_index(st)
+    assert torch.equal(idx, bench.arena_sample_index(st)) and bool((idx[1:] > idx[:-1]).all())
+    for _, _, off, n, _ in st.entries:
+        got = int(((idx >= off) & (idx < off + n)).sum())
+        assert got == min(n, bench.DUMP_PER_TENSOR)
+    arrays = bench.training_outputs(model, torch.tensor(1.5))
+    bench.write_outputs(str(tmp_path / "out"), arrays)
+    files = sorted(os.listdir(tmp_path / "out"))
+    assert files == ["grads.npy", "loss.npy", "params.npy"]
+    assert sum(os.path.getsize(tmp_path / "out" / f) for f in files) <= bench.DUMP_LIMIT_BYTES
+    for k, v in arrays.items():
+        a = np.load(tmp_path / "out" / (k + ".npy"))
+        assert a.dtype == np.float32 and np.array_equal(a, v.numpy())
+    assert np.array_equal(np.load(tmp_path / "out" / "params.npy"), st.flat[idx].numpy())
+    bench.DUMP_LIMIT_BYTES = 1024
+    with pytest.raises(RuntimeError, match="limit"):
+        bench.write_outputs(str(tmp_path / "big"), arrays)
+    assert not os.path.exists(tmp_path / "big")

@@ -19,7 +19,7 @@ elif [ "$TESTS" == "full" ]; then
   timeout 900 python -m pytest tests -m gpu -q -rfE --tb=short > $O/pytest.log 2>&1
   echo "pytest rc=$?" >> $O/pytest.log; grep -E "passed|failed|FAILED|Error|rc=" $O/pytest.log | tail -n 8
 fi
-B="python bench.py --steps 8 --warmup 3 --no-cpu-baseline --variant-steps 0"
+B="python bench.py --full --steps 8 --warmup 3 --no-cpu-baseline --variant-steps 0"
 run() {  # name, env assignments...
   name=$1; shift
   extra=""
