@@ -183,12 +183,14 @@ def depth_grad_loss(pred_depth, gt_depth, gt_raydrop, patch_size, scale, alpha_g
     return loss
 
 
-def process_pointcloud(dataset, ground_split=None):
+def process_pointcloud(dataset, ground_split=None, removal=None):
     """runner.py:923-951 on the device: per frame, ground-truth range image -> points (lidar4d_amd.convert) -> split into
     non-ground / ground -> scene units and world frame.  Returns (pc_list, pc_ground_list), dicts keyed by str(frame).
-    The reference separates the ground with RANSAC + open3d outlier removal (utils/misc.py:128-154), which is dataset
-    preprocessing and out of scope; ``ground_split(points[N,3]) -> bool mask`` stands in for it (default: within 0.15 m
-    of the synthetic scene's ground plane z = -1.7 m, the reference's RANSAC distance threshold)."""
+    The reference separates the ground with RANSAC + open3d outlier removal (utils/misc.py:128-154):
+    ``removal(points[N,3]) -> (non_ground, ground)`` does that when given -- ``lidar4d_amd.pointprep.point_removal`` is the
+    device-side counterpart, the choice for a real sequence -- and takes precedence over ``ground_split``.  Without it,
+    ``ground_split(points[N,3]) -> bool mask`` stands in (default: within 0.15 m of the synthetic scene's ground plane
+    z = -1.7 m, the reference's RANSAC distance threshold)."""
     from .convert import pano_to_lidar
     if ground_split is None:
         ground_split = lambda pts: (pts[:, 2] + 1.7).abs() < 0.15
@@ -197,9 +199,14 @@ def process_pointcloud(dataset, ground_split=None):
         img = dataset.images[k]
         gt_depth = img[..., 2] * img[..., 0]
         pts = pano_to_lidar(gt_depth / dataset.scale, dataset.fov)          # metres, sensor frame
-        is_ground = ground_split(pts)
         pose = dataset.poses[k]
         to_world = lambda q: (q * dataset.scale) @ pose[:3, :3].T + pose[:3, 3]
+        if removal is not None:
+            non_ground, ground = removal(pts)
+            pc_list[f"{k}"] = to_world(non_ground).contiguous()
+            pc_ground_list[f"{k}"] = to_world(ground).contiguous()
+            continue
+        is_ground = ground_split(pts)
         pc_list[f"{k}"] = to_world(pts[~is_ground]).contiguous()
         pc_ground_list[f"{k}"] = to_world(pts[is_ground]).contiguous()
     return pc_list, pc_ground_list
@@ -716,14 +723,16 @@ class Trainer:
     def __init__(self, model, dataset, lr=1e-2, iters=30000, num_steps=768, chamfer=True, flow=True, urf=False,
                  ema_decay=None, loss_scaler=True, init_scale=65536.0, depth_loss="l1", raydrop_loss="mse",
                  intensity_loss="mse", epoch_steps=None, fused_losses=True, force_allreduce=False, overlap_allreduce=True,
-                 grad_transport="fp32", graph_batch_inside=True, flow_loss_stream=True):
+                 grad_transport="fp32", graph_batch_inside=True, flow_loss_stream=True, point_removal=None):
         """Defaults follow the reference's default run: the ray chamfer term is always part of its step
         (runner.py:215-220) and ``--flow_loss`` defaults to True (main_lidar4d.py:67).
         chamfer: a mean over the rank's own rays, so under data parallelism it is scaled by 1/world before the SUM
         all-reduce.  flow: the scene-flow consistency term (runner.py:222-253), a per-frame sum, enters each
         rank's loss as it is (every rank works on its own frame).  loss_scaler: GradScaler semantics on the device
         (DynamicLossScaler).  ema_decay: parameter EMA, updated once per epoch like the reference's (runner.py:534-535);
-        an epoch = ``epoch_steps`` steps (default: one per training frame, the reference's loader length)."""
+        an epoch = ``epoch_steps`` steps (default: one per training frame, the reference's loader length).
+        point_removal: ``removal`` of process_pointcloud for the scene-flow clouds (``lidar4d_amd.pointprep.point_removal`` on a
+        real sequence); None keeps the synthetic scene's ground split."""
         self.model, self.dataset, self.num_steps, self.chamfer = model, dataset, num_steps, chamfer
         self.flow, self.urf, self.iters = flow, urf, iters
         self.loss_kinds = dict(depth_loss=depth_loss, raydrop_loss=raydrop_loss, intensity_loss=intensity_loss)
@@ -740,7 +749,7 @@ class Trainer:
         self.epoch_steps = epoch_steps if epoch_steps is not None else getattr(dataset, "num_frames", 1)
         self.local_step = 0
         if flow:
-            self.pc_list, self.pc_ground_list = process_pointcloud(dataset)
+            self.pc_list, self.pc_ground_list = process_pointcloud(dataset, removal=point_removal)
         self.opt = FlatAdam(model, lr=lr, iters=iters)
         self.scaler = DynamicLossScaler(model._store.flat.device, init_scale=init_scale) if loss_scaler else None
         model.reference_grad_none = False  # untouched time slices are gated on the device (FlatAdam), no host read-back
