@@ -847,15 +847,9 @@ extern "C" int64_t l4d_density_encode_bwd_workspace(const l4d_field_desc* f, int
 extern "C" int l4d_density_encode_bwd(const l4d_field_desc* f, const l4d_field_grads* g, const float* xt, const void* flow16,
                                       const float* tinfo, int64_t P, const void* dX, int32_t in_pad, float param_scale,
                                       const float* plane_abs_max, int32_t samples_per_ray, void* workspace, void* dflow16,
-                                      float* plane_rows, const float* gd_absmax, int32_t defer_join, void* stream_) {
+                                      float* plane_rows, const float* gd_absmax, void* stream_) {
   if (P == 0) return 0;
   hipStream_t stream = (hipStream_t)stream_;
-  // Independent parts of the adjoint on side streams (l4d_streams_config bit 1): the sorted scatter of the static grid
-  // (HBM-streaming + LDS ranking) needs dX only; the static-plane and dynamic-hash adjoints (LDS atomics) need the prep
-  // kernel's outputs; the time planes (VALU-bound) stay on the launch stream -- they produce d(flow), which the caller's flow
-  // network backward waits for.  The kernels are bound by different units and share the chip instead of queueing.
-  const bool forked = (l4d_streams_mask() & 2) && P >= (1 << 18);
-  hipStream_t s_bins = stream, s_lds = stream;
   FieldDesc d;
   if (make_field(f, d)) return 1;
   FieldGrads fg;
@@ -865,18 +859,10 @@ extern "C" int l4d_density_encode_bwd(const l4d_field_desc* f, const l4d_field_g
   fg.planes_cl = g->planes_cl;
   const int L3 = d.hd[0].n_levels + d.hd[1].n_levels + d.hd[2].n_levels;
   if (ST_DYN_MAX + L3 > ST_SIZE) { l4d_set_error(1, "l4d_density_encode_bwd: too many dynamic hash levels"); return 1; }
-  {  // everything that can be rejected is rejected BEFORE the first side stream is forked (an error return behind a
-    // fork left that stream un-joined -- under capture an unjoined fork, in eager mode later work not ordered behind it)
-    int lds_t = 0;
-    for (int s = 0; s < d.planes.n_scales; ++s)
-      for (int j = 0; j < 3; ++j) lds_t += TFRAMES * d.planes.res[s][j] * 8 * 4;
-    if (lds_t > 160 * 1024) { l4d_set_error(1, "l4d_density_encode_bwd: time planes exceed LDS"); return 1; }
-  }
-  // error returns behind a fork join what was forked, so that the launch stream is ordered behind the side streams' work again
-  auto fail = [&](int rc) -> int {
-    if (forked) { (void)l4d_side_join(stream_, 1); (void)l4d_side_join(stream_, 2); }
-    return rc;
-  };
+  int lds_planes = 0;  // the time-plane kernel's accumulators: checked in front of the first launch
+  for (int s = 0; s < d.planes.n_scales; ++s)
+    for (int j = 0; j < 3; ++j) lds_planes += TFRAMES * d.planes.res[s][j] * 8 * 4;
+  if (lds_planes > 160 * 1024) { l4d_set_error(1, "l4d_density_encode_bwd: time planes exceed LDS"); return 1; }
   const WorkLayout w = work_layout(f, P);
   char* ws = (char*)workspace;
   float* stats = (float*)(ws + w.stats);
@@ -890,38 +876,24 @@ extern "C" int l4d_density_encode_bwd(const l4d_field_desc* f, const l4d_field_g
 
   // static 3-D hash grid: sorted scatter of dX[:, 2*nS*8 + lvl*4 ..] (binscatter.hip)
   {
-    if (forked) {
-      s_bins = (hipStream_t)l4d_side_fork(stream_, 1);
-      if (!s_bins) return fail(1);
-    }
     const int cols3[3] = {0, 1, 2};
     int rc = bs_scatter(d.hs, 3, 4, xt, P, 4, cols3, (const half_t*)dX, in_pad, 2 * d.planes.n_scales * 8, 1.0f, fg.hs_table,
-                        param_scale, ws + w.bins, s_bins);
-    if (rc) return fail(rc);
+                        param_scale, ws + w.bins, stream);
+    if (rc) return rc;
   }
   // With the largest |dX| of the time-plane columns known beforehand (gd_absmax, from the sigma network's backward) the prep
   // kernel's work is done by the time-plane kernel itself (planes_dyn_lds_kernel<.., PREP = true>).
   const int colsA_ = 2 * d.planes.n_scales * 8, colD_ = colsA_ + d.hs.n_levels * 4;
   const bool fused_prep = gd_absmax && plane_rows && colD_ % 8 == 0 && L3 % 8 == 0 && L3 <= 48 && in_pad % 8 == 0;
-  const bool prep_side = false;  // (the preparation kernel on the side stream of its consumers: measured no gain in round 4, switch removed)
-  if (fused_prep || prep_side) {
+  if (fused_prep) {
     l4d_copy_words_async(stats + ST_GD_MAX, gd_absmax, 1, stream);
-  }
-  if (prep_side) {
-    s_lds = (hipStream_t)l4d_side_fork(stream_, 2);
-    if (!s_lds) return fail(1);
-  }
-  if (!fused_prep) {
+  } else {
     const int staged = (colD_ % 8 == 0 && L3 % 8 == 0) ? 1 : 0;  // 16-byte pieces
     const int lds = staged ? PREP_THREADS * (colsA_ + L3 + 8) * 2 : 0;
-    L4D_LAUNCH(field_bwd_prep_kernel, dim3((unsigned)ceil_div64(P, PREP_THREADS)), dim3(PREP_THREADS), lds, prep_side ? s_lds : stream, d, xt, tinfo, P,
+    L4D_LAUNCH(field_bwd_prep_kernel, dim3((unsigned)ceil_div64(P, PREP_THREADS)), dim3(PREP_THREADS), lds, stream, d, xt, tinfo, P,
                (const half_t*)dX, in_pad, param_scale, gvs, gdynT, stats, staged, xsoa, segb);
   }
 
-  if (forked && !fused_prep && !prep_side) {  // after the prep kernel
-    s_lds = (hipStream_t)l4d_side_fork(stream_, 2);
-    if (!s_lds) return fail(1);
-  }
   // chunking: one chunk per workgroup column; few enough chunks that the flush traffic stays small
   // (one chunk per CU from 2,048 samples per chunk on: at the reference's own batch of 1,024 rays -- 786 k samples -- the former
   // rule of >= 8,192 samples per chunk left 96 workgroups for 256 CUs in the time-plane kernel, whose grid is the chunks)
@@ -946,10 +918,7 @@ extern "C" int l4d_density_encode_bwd(const l4d_field_desc* f, const l4d_field_g
 
   // time planes
   {
-    int lds = 0;
-    for (int s = 0; s < d.planes.n_scales; ++s)
-      for (int j = 0; j < 3; ++j) lds += TFRAMES * d.planes.res[s][j] * 8 * 4;
-    if (lds > 160 * 1024) { l4d_set_error(1, "l4d_density_encode_bwd: time planes exceed LDS"); return fail(1); }  // (checked above)
+    const int lds = lds_planes;
     const PlaneRows pr = make_plane_rows(d, plane_rows);
     const PrepOut po{gvs, gdynT, xsoa, stats, wave_skip ? segb : nullptr};  // (read only under wave_skip; chunks of another size do not start on segments)
     if (plane_rows) {
@@ -973,10 +942,6 @@ extern "C" int l4d_density_encode_bwd(const l4d_field_desc* f, const l4d_field_g
                  P, chunk, (const half_t*)dX, in_pad, param_scale, stats, (half_t*)dflow16, pr, po);
     }
   }
-  if (forked && fused_prep) {  // the static-plane / dynamic-hash adjoints need what the fused kernel wrote
-    s_lds = (hipStream_t)l4d_side_fork(stream_, 2);
-    if (!s_lds) return fail(1);
-  }
   // static planes
   {
     BandTasks t;
@@ -990,14 +955,14 @@ extern "C" int l4d_density_encode_bwd(const l4d_field_desc* f, const l4d_field_g
         int rows = std::max(1, (PLANES_BAND_KB * 1024) / (W * 8 * 4));
         rows = std::min(rows, H);
         for (int r0 = 0; r0 < H; r0 += rows) {
-          if (t.n >= MAX_TASKS) { l4d_set_error(1, "l4d_density_encode_bwd: too many plane bands"); return fail(1); }
+          if (t.n >= MAX_TASKS) { l4d_set_error(1, "l4d_density_encode_bwd: too many plane bands"); return 1; }
           t.s[t.n] = s; t.j[t.n] = j; t.row0[t.n] = r0; t.nrows[t.n] = std::min(rows, H - r0);
           max_lds = std::max(max_lds, t.nrows[t.n] * W * 8 * 4);
           ++t.n;
         }
       }
     (void)hipFuncSetAttribute((const void*)planes_static_lds_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, max_lds);
-    L4D_LAUNCH(planes_static_lds_kernel, dim3(n_chunks_ps, t.n), dim3(1024), max_lds, s_lds, d, t, fg.planes_cl, xsoa, P, chunk_ps,
+    L4D_LAUNCH(planes_static_lds_kernel, dim3(n_chunks_ps, t.n), dim3(1024), max_lds, stream, d, t, fg.planes_cl, xsoa, P, chunk_ps,
                        wave_skip, gvs, param_scale, stats, wave_skip ? segb : nullptr);
   }
   // dynamic hash
@@ -1028,7 +993,7 @@ extern "C" int l4d_density_encode_bwd(const l4d_field_desc* f, const l4d_field_g
           // one per index range (four each); L4D_DH_PARITY=0: the range form (A/B switch, tests/test_gpu_switches.py)
           if (dh_parity && size == 2 * max_entries && is_pow2((uint32_t)size) && ((d.hd[p].hashed_mask >> l) & 1u)) {
             for (int par = 0; par < 2; ++par) {
-              if (t.n >= MAX_TASKS) { l4d_set_error(1, "l4d_density_encode_bwd: too many hash tasks"); return fail(1); }
+              if (t.n >= MAX_TASKS) { l4d_set_error(1, "l4d_density_encode_bwd: too many hash tasks"); return 1; }
               t.plane[t.n] = p; t.lvl[t.n] = l; t.lo[t.n] = -1 - par; t.cnt[t.n] = size / 2;
               t.hoff[t.n] = hoff_plane[p] + (int)d.hd[p].offset[l];
               ++t.n;
@@ -1037,7 +1002,7 @@ extern "C" int l4d_density_encode_bwd(const l4d_field_desc* f, const l4d_field_g
             continue;
           }
           for (int lo = 0; lo < size; lo += max_entries) {
-            if (t.n >= MAX_TASKS) { l4d_set_error(1, "l4d_density_encode_bwd: too many hash tasks"); return fail(1); }
+            if (t.n >= MAX_TASKS) { l4d_set_error(1, "l4d_density_encode_bwd: too many hash tasks"); return 1; }
             t.plane[t.n] = p; t.lvl[t.n] = l; t.lo[t.n] = lo; t.cnt[t.n] = std::min(max_entries, size - lo);
             t.hoff[t.n] = hoff_plane[p] + (int)d.hd[p].offset[l];
             ++t.n;
@@ -1045,20 +1010,15 @@ extern "C" int l4d_density_encode_bwd(const l4d_field_desc* f, const l4d_field_g
         }
       if (t.n == 0) continue;
       (void)hipFuncSetAttribute((const void*)dynhash_lds_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 128 * 1024);
-      L4D_LAUNCH(dynhash_lds_kernel, dim3(n_chunks_dh, t.n), dim3(1024), lds_kb * 1024, s_lds, d, t, xsoa, P, chunk_dh, gdynT, stats, Hbuf);
+      L4D_LAUNCH(dynhash_lds_kernel, dim3(n_chunks_dh, t.n), dim3(1024), lds_kb * 1024, stream, d, t, xsoa, P, chunk_dh, gdynT, stats, Hbuf);
     }
     for (int p = 0; p < 3; ++p) {
       unsigned max_size = 0;
       for (int l = 0; l < d.hd[p].n_levels; ++l) max_size = std::max(max_size, d.hd[p].size[l]);
-      L4D_LAUNCH(dynhash_expand_kernel, dim3((max_size + 255) / 256, d.hd[p].n_levels), dim3(256), 0, s_lds, d, fg, tinfo,
+      L4D_LAUNCH(dynhash_expand_kernel, dim3((max_size + 255) / 256, d.hd[p].n_levels), dim3(256), 0, stream, d, fg, tinfo,
                          Hbuf, p, hoff_plane[p], param_scale, parity_levels[p]);
     }
   }
   L4D_LAUNCH_CHECK("l4d_density_encode_bwd");
-  if (forked && !defer_join) {
-    int rc = l4d_side_join(stream_, 1);
-    if (!rc) rc = l4d_side_join(stream_, 2);
-    if (rc) return rc;
-  }
   return 0;
 }

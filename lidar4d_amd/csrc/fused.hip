@@ -56,12 +56,7 @@ __device__ __forceinline__ void store8h(half_t* dst, const float v[8]) {
 #define ENC_THREADS 64  // one wave per workgroup: measured best (64: 13.8 ms, 128: 14.1, 256: 14.5 for the entry point)
 #define ENC_MAX_IN_PAD 192  // widest network input row (BASELINE config C2: L = 16 hash levels -> 176 columns)
 #define ENC_WAVES_PER_EU 2
-#define ENC_SPLIT_MIN_POINTS (1 << 18)  // below this the extra launch and the re-read of xt / flow cost more than the overlap buys
-#define ENC_WAVES_PER_EU_HASH 4
-// PART: 0 = the whole row in one kernel; 1 = the plane columns [0, 2 nS C) only; 2 = everything behind them (hash grids, ones).
-// The split (l4d_density_encode_fwd with side streams) exists for two reasons: the plane part does not need the xz / yz columns
-// that dynhash_fwd_lds_kernel produces, so the two run CONCURRENTLY (texel-bandwidth-bound next to VALU / LDS-bound), and the
-// hash part alone needs half the registers, i.e. twice the wavefronts to hide its L2-missing gathers behind.
+#define ENC_HS_PRE_MIN_POINTS (1 << 18)  // static grid's level-major pre-pass: below this its extra launch and its re-read of xt cost more than it saves
 // HSMODE 1: the static grid's columns come from the level-major pre-pass (hashgrid.hip hashgrid_fwd_levels_kernel, hsT[level][P][4]
 // fp16) instead of being gathered here: 8 bytes per level and sample, dense, and the kernel's own gathers (xy stack, planes) no
 // longer share the L2s with 33 MB of static tables.  HSMODE 2: gathered here, x-neighbour pairs in one 16-byte load where they
@@ -113,15 +108,16 @@ extern "C" int l4d_debug_enc_phase_clk(unsigned long long* out_dev, int reset, v
 #define ENC_CLK(i)
 #define ENC_CLK_FLUSH
 #endif
+// PART is always 0 (the whole row in one kernel): it stays in the signature because profiles and bench.py key kernels by their launch-site names
 template <bool USE_HDT, bool ROWS, int PART = 0, int HSMODE = 0, bool SIGMA = false>
-__global__ void __launch_bounds__(SIGMA ? ENC_SIGMA_THREADS : ENC_THREADS) __attribute__((amdgpu_waves_per_eu(PART == 2 ? ENC_WAVES_PER_EU_HASH : ENC_WAVES_PER_EU, 8))) density_encode_fwd_kernel(FieldDesc fd, const float* __restrict__ xt,
+__global__ void __launch_bounds__(SIGMA ? ENC_SIGMA_THREADS : ENC_THREADS) __attribute__((amdgpu_waves_per_eu(ENC_WAVES_PER_EU, 8))) density_encode_fwd_kernel(FieldDesc fd, const float* __restrict__ xt,
                                                                         const half_t* __restrict__ flow16,
                                                                         const float* __restrict__ tinfo, int64_t P,
                                                                         const half_t* __restrict__ hdT,
                                                                         half_t* __restrict__ X, int in_pad, PlaneRows prows,
                                                                         const half_t* __restrict__ hsT, SigmaOut so) {
   constexpr int C = 8;
-  static_assert(!SIGMA || PART == 0, "the network epilogue needs the whole row");
+  static_assert(PART == 0, "the row is no longer computed in parts");
   // the row is staged and written out in two parts (planes | everything else) so that the staging buffer is half as
   // large: LDS is what limits this kernel's occupancy (gather latency needs waves in flight).  (SIGMA: the whole row at once.)
   extern __shared__ __attribute__((aligned(16))) half_t stage_all[];  // (SIGMA: 18 weight fragments, then) [threads][pitch]
@@ -206,7 +202,7 @@ __global__ void __launch_bounds__(SIGMA ? ENC_SIGMA_THREADS : ENC_THREADS) __att
     asm volatile("" ::: "memory");  // (the requests stay up here)
   }
   // ---- hex-planes (planes_field.py:87-141; blend lidar4d.py:175) ----
-  for (int s = 0; PART != 2 && s < nS; ++s) {
+  for (int s = 0; s < nS; ++s) {
     float ps[C], d0[C], d1[C], d2[C];
     planes_group<C>(fd, s, x0, false, ps);
 #ifdef ENC_PHASE_CLOCK
@@ -248,10 +244,9 @@ __global__ void __launch_bounds__(SIGMA ? ENC_SIGMA_THREADS : ENC_THREADS) __att
       }
     }
   };
-  if (PART != 2 && !SIGMA) {
+  if (!SIGMA) {
     __syncthreads();
     copy_out(0, colsA);
-    if (PART == 1) return;
     __syncthreads();
   }
   if (!SIGMA) row -= colsA;  // the second part is staged from column 0 again
@@ -663,7 +658,7 @@ static inline int64_t enc_ws_hs_offset(const l4d_field_desc* f, int64_t P) {
 }
 // (the static grid's columns only where the pre-pass can run: F = 4 and enough points -- 0.8 GB at 12.6 M samples otherwise unused)
 extern "C" int64_t l4d_density_encode_fwd_workspace(const l4d_field_desc* f, int64_t P) {
-  const bool hs_cols = f->hash_static.n_features == 4 && P >= ENC_SPLIT_MIN_POINTS;
+  const bool hs_cols = f->hash_static.n_features == 4 && P >= ENC_HS_PRE_MIN_POINTS;
   return enc_ws_hs_offset(f, P) + (hs_cols ? (int64_t)f->hash_static.n_levels * P * 8 : 0);
 }
 
@@ -705,17 +700,8 @@ static int encode_fwd_impl(const l4d_field_desc* f, const float* xt, const void*
     return 1;
   }
   hipStream_t main_s = (hipStream_t)stream;
-  // side stream: the LDS evaluation of the xz / yz stacks runs next to the plane part of the encode (l4d_streams_config bit 0)
-  // static grid: level-major pre-pass into the workspace (needs the workspace, F = 4 and the one-kernel form of the encode);
-  // l4d_streams_config bit 2: that pre-pass (L2 gathers) runs NEXT TO the LDS kernel (VALU / LDS-bound) instead of behind it
-  const bool hs_pre = hd_scratch && plane_rows && !(l4d_streams_mask() & 1) && enc_hs_split() && f->hash_static.n_features == 4 && P >= ENC_SPLIT_MIN_POINTS;
-  const bool hs_side = hs_pre && (l4d_streams_mask() & 4);
-  const bool split = hd_scratch && (l4d_streams_mask() & 1) && P >= ENC_SPLIT_MIN_POINTS;
-  hipStream_t dh_s = main_s;
-  if (split || hs_side) {
-    dh_s = (hipStream_t)l4d_side_fork(stream, 0);
-    if (!dh_s) return 1;
-  }
+  // static grid: level-major pre-pass into the workspace (needs the workspace, the time-plane rows, F = 4 and enough points)
+  const bool hs_pre = hd_scratch && plane_rows && enc_hs_split() && f->hash_static.n_features == 4 && P >= ENC_HS_PRE_MIN_POINTS;
   if (hd_scratch) {
     if (d.hd[1].size[d.hd[1].n_levels - 1] > DH_MAX_ENTRIES || d.hd[2].size[d.hd[2].n_levels - 1] > DH_MAX_ENTRIES) {
       l4d_set_error(1, "l4d_density_encode_fwd: xz/yz slice tables exceed the LDS staging size; pass hd_scratch = null");
@@ -728,16 +714,14 @@ static int encode_fwd_impl(const l4d_field_desc* f, const float* xt, const void*
     const int64_t n_dyn = d.hd[0].n_levels + d.hd[1].n_levels + d.hd[2].n_levels;
     float* xs = (float*)((char*)hd_scratch + (n_dyn * P * 2 + 255) / 256 * 256);
     half_t* flowT = (half_t*)((char*)xs + (3 * P * 4 + 255) / 256 * 256);
-    L4D_LAUNCH(warp_coords_kernel, dim3((unsigned)ceil_div64(P, 256)), dim3(256), 0, dh_s, xt, (const half_t*)flow16, P, xs, flowT);
+    L4D_LAUNCH(warp_coords_kernel, dim3((unsigned)ceil_div64(P, 256)), dim3(256), 0, main_s, xt, (const half_t*)flow16, P, xs, flowT);
     L4D_LAUNCH(dynhash_fwd_lds_kernel, dim3(n_chunks, d.hd[1].n_levels + d.hd[2].n_levels), dim3(DH_THREADS),
-               2 * DH_MAX_ENTRIES * 8, dh_s, d, xs, flowT, tinfo, P, chunk, (half_t*)hd_scratch);
+               2 * DH_MAX_ENTRIES * 8, main_s, d, xs, flowT, tinfo, P, chunk, (half_t*)hd_scratch);
   }
   half_t* hsT = hs_pre ? (half_t*)((char*)hd_scratch + enc_ws_hs_offset(f, P)) : nullptr;
   if (hs_pre) {
     const int cols3[3] = {0, 1, 2};
-    const int rc = l4d_hashgrid_levels_launch(&d.hs, 3, 4, xt, P, 4, cols3, d.hs_table, hsT, main_s);
-    if (hs_side && l4d_side_join(stream, 0)) return 1;  // (also on the error path: the launch stream is ordered behind the side stream again)
-    if (rc) return 1;
+    if (l4d_hashgrid_levels_launch(&d.hs, 3, 4, xt, P, 4, cols3, d.hs_table, hsT, main_s)) return 1;
   }
   const PlaneRows pr = make_plane_rows(d, plane_rows);
   if (plane_rows)  // tinfo[0..2] = t, t1, t2: frames without a neighbour get a row nobody reads
@@ -745,8 +729,8 @@ static int encode_fwd_impl(const l4d_field_desc* f, const float* xt, const void*
   const dim3 egrid((unsigned)xcd_grid(ceil_div64(P, ENC_THREADS)));
   const int colsA = 2 * d.planes.n_scales * 8;
   const int enc_lds = ENC_THREADS * (std::max(colsA, in_pad - colsA) + 8) * 2;
-#define ENC_LAUNCH(HDT, ROWS, PART)                                                                                         \
-  L4D_LAUNCH((density_encode_fwd_kernel<HDT, ROWS, PART>), egrid, dim3(ENC_THREADS), enc_lds, main_s, d, xt,                \
+#define ENC_LAUNCH(HDT, ROWS)                                                                                               \
+  L4D_LAUNCH((density_encode_fwd_kernel<HDT, ROWS, 0>), egrid, dim3(ENC_THREADS), enc_lds, main_s, d, xt,                   \
              (const half_t*)flow16, tinfo, P, (const half_t*)hd_scratch, (half_t*)X, in_pad, pr, (const half_t*)nullptr, no_sigma)
   const SigmaOut no_sigma{nullptr, nullptr, nullptr, nullptr, 0};
   // the density network as the kernel's epilogue: the default network shape behind the level-major form of the encode
@@ -773,19 +757,13 @@ static int encode_fwd_impl(const l4d_field_desc* f, const float* xt, const void*
   } else if (hs_pre) {
     L4D_LAUNCH((density_encode_fwd_kernel<true, true, 0, 1>), egrid, dim3(ENC_THREADS), enc_lds, main_s, d, xt,
                (const half_t*)flow16, tinfo, P, (const half_t*)hd_scratch, (half_t*)X, in_pad, pr, (const half_t*)hsT, no_sigma);
-  } else if (!split && hd_scratch && plane_rows && l4d_hs_pair_ok(&d.hs, f->hash_static.n_features, d.hs_table)) {
+  } else if (hd_scratch && plane_rows && l4d_hs_pair_ok(&d.hs, f->hash_static.n_features, d.hs_table)) {
     L4D_LAUNCH((density_encode_fwd_kernel<true, true, 0, 2>), egrid, dim3(ENC_THREADS), enc_lds, main_s, d, xt,
                (const half_t*)flow16, tinfo, P, (const half_t*)hd_scratch, (half_t*)X, in_pad, pr, (const half_t*)nullptr, no_sigma);
-  } else if (split) {  // plane columns while the side stream evaluates the xz / yz stacks, then the hash columns
-    if (plane_rows) ENC_LAUNCH(true, true, 1);
-    else ENC_LAUNCH(true, false, 1);
-    if (l4d_side_join(stream, 0)) return 1;
-    if (plane_rows) ENC_LAUNCH(true, true, 2);
-    else ENC_LAUNCH(true, false, 2);
-  } else if (hd_scratch && plane_rows) ENC_LAUNCH(true, true, 0);
-  else if (hd_scratch) ENC_LAUNCH(true, false, 0);
-  else if (plane_rows) ENC_LAUNCH(false, true, 0);
-  else ENC_LAUNCH(false, false, 0);
+  } else if (hd_scratch && plane_rows) ENC_LAUNCH(true, true);
+  else if (hd_scratch) ENC_LAUNCH(true, false);
+  else if (plane_rows) ENC_LAUNCH(false, true);
+  else ENC_LAUNCH(false, false);
 #undef ENC_LAUNCH
   L4D_LAUNCH_CHECK("l4d_density_encode_fwd");
   if (so && !sigma_fused)  // other shapes / paths: the network as a launch of its own on the rows just written

@@ -832,7 +832,7 @@ class Trainer:
             # torch's capture recipe: the warm-up step runs on the (non-default) stream the capture will use, and nothing of
             # its autograd graph survives it -- an AccumulateGrad node that was created on the legacy default stream and is
             # still alive makes the captured backward synchronise with that stream, which a capture cannot contain.  The
-            # library's side streams, when switched on, fork and join by events and are captured like any other dependency.
+            # library launches on the caller's stream only, so the render path is captured as one chain of kernels.
             side = st.setdefault("stream", torch.cuda.Stream())
             side.wait_stream(torch.cuda.current_stream())
             with torch.cuda.stream(side):
