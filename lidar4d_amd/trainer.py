@@ -953,3 +953,59 @@ class Trainer:
             pred_intensity = pred_intensity * raydrop_mask
             pred_depth = pred_depth * raydrop_mask
         return pred_raydrop, pred_intensity, pred_depth
+
+    @torch.no_grad()
+    def evaluate(self, frames=None, refine=True, max_ray_batch=4096, raydrop_loss="mse", intensity_scale=1.0, raydrop_ratio=0.5,
+                 lpips_fn=None):
+        """runner.py:379-434,553-682 without the PNG, progress-bar and tensorboard output: every frame (default: all of the
+        dataset's) is rendered on the EMA weights if there are any, scored by the evaluation loss of runner.py:418-422 (the
+        trainer's criteria, the reference's default weights 1 / 0.01 / 0.1) and fed to the four meters of
+        main_lidar4d.py:199-204 in their order.  Intensity, depth and points meters see the predictions masked by
+        ``pred_raydrop > 0.5``.  The raw weights are back in place afterwards.
+        Returns dict(loss = mean evaluation loss, raydrop / intensity / depth / points = each meter's measure(), report = the
+        four report() lines).  The image meters and the loss read nothing back from the device before the final measure() calls;
+        PointsMeter reads the sizes of its two clouds per frame, as it always has."""
+        from .metrics import DepthMeter, IntensityMeter, PointsMeter, RaydropMeter
+        scale = self.dataset.scale
+        meters = {"raydrop": RaydropMeter(ratio=raydrop_ratio),
+                  "intensity": IntensityMeter(scale=intensity_scale, lpips_fn=lpips_fn),
+                  "depth": DepthMeter(scale=scale, lpips_fn=lpips_fn),
+                  "points": PointsMeter(scale=scale, intrinsics=self.dataset.fov)}
+        crit = {k: criterion(self.loss_kinds[f"{k}_loss"], scale) for k in ("depth", "raydrop", "intensity")}
+        alpha_d, alpha_r, alpha_i = 1.0, 0.01, 0.1  # main_lidar4d.py's defaults, as in lidar_loss
+        was_training = self.model.training
+        self.model.eval()
+        if self.ema is not None:  # runner.py:565-567
+            self.ema.store()
+            self.ema.copy_to()
+        try:
+            total, count = None, 0
+            for k in (range(self.dataset.num_frames) if frames is None else frames):
+                fr = self.dataset.frame(k)
+                pred_raydrop, pred_intensity, pred_depth = self.test_step(fr, refine=refine, max_ray_batch=max_ray_batch,
+                                                                          raydrop_loss=raydrop_loss, alpha_r=0)  # unmasked
+                images = fr["images_lidar"]
+                gt_raydrop = images[:, :, :, 0]
+                gt_intensity = images[:, :, :, 1] * gt_raydrop
+                gt_depth = images[:, :, :, 2] * gt_raydrop
+                preds_mask = torch.where(pred_raydrop > 0.5, 1, 0)
+                masked_intensity, masked_depth = pred_intensity * preds_mask, pred_depth * preds_mask
+                loss = (alpha_d * crit["depth"](masked_depth, gt_depth).mean()
+                        + alpha_r * crit["raydrop"](pred_raydrop, gt_raydrop).mean()
+                        + alpha_i * crit["intensity"](masked_intensity, gt_intensity).mean())
+                total = loss if total is None else total + loss
+                count += 1
+                meters["raydrop"].update(pred_raydrop, gt_raydrop)
+                meters["intensity"].update(masked_intensity, gt_intensity)
+                meters["depth"].update(masked_depth, gt_depth)
+                meters["points"].update(masked_depth, gt_depth)
+        finally:
+            if self.ema is not None:  # runner.py:679-680
+                self.ema.restore()
+            self.model.train(was_training)
+        if count == 0:
+            raise ValueError("evaluate: no frames")
+        result = {name: m.measure() for name, m in meters.items()}
+        result["report"] = [m.report() for m in meters.values()]
+        result["loss"] = float((total / count).item())
+        return result
