@@ -127,6 +127,56 @@ def urf_loss(outputs, gt_depth, global_step, iters):
     return 0.1 * loss_empty + 0.1 * loss_near
 
 
+class _LineOfSightLossFn(torch.autograd.Function):
+    """``urf_loss`` as one autograd node on csrc/losses.hip (liblidar4d_loss.so, include/lidar4d_loss.h): forward =
+    l4dl_los_fwd (three launches), backward = l4dl_los_bwd (two) with the upstream gradient as a device pointer.  Saves the two
+    inputs and nothing else of size [N, T]; the tolerance comes from ``sched[0]`` on the device when a schedule is given, so
+    nothing in the node needs the host."""
+
+    @staticmethod
+    def forward(ctx, weights, z_vals, gt_depth, step, iters, sched):
+        from . import _loss_lib
+        for t, name in ((weights, "weights"), (z_vals, "z_vals"), (gt_depth, "gt_depth"), (sched, "sched")):
+            ops._chk(t, None, name)
+        N, T = int(z_vals.shape[0]), int(z_vals.shape[1])
+        w = weights.detach().to(torch.float32).reshape(N, T).contiguous()
+        z = z_vals.detach().to(torch.float32).reshape(N, T).contiguous()
+        d = gt_depth.detach().reshape(-1)
+        d = (d if d.dtype == torch.float16 else d.to(torch.float32)).contiguous()
+        if d.numel() != N:
+            raise ValueError(f"line_of_sight_loss: {d.numel()} depths for {N} rays")
+        if sched is not None:
+            ops._chk(sched, torch.float32, "sched")
+        args = (ops._p(w), ops._p(z), ops._p(d), int(d.dtype == torch.float16), N, T, ops._p(sched), int(step), int(iters))
+        loss = torch.empty(1, dtype=torch.float32, device=w.device)
+        ws = torch.empty(max(8, int(_loss_lib.lib().l4dl_los_workspace(N, T))), dtype=torch.uint8, device=w.device)
+        _loss_lib.call("l4dl_los_fwd", *args, ops._p(loss), ops._p(ws), ops._stream())
+        ctx.save_for_backward(w, z, d)
+        ctx.sched, ctx.step, ctx.iters, ctx.shape = sched, int(step), int(iters), weights.shape
+        return loss.reshape(())
+
+    @staticmethod
+    def backward(ctx, g):
+        from . import _loss_lib
+        w, z, d = ctx.saved_tensors
+        N, T = z.shape
+        gs = g.detach().to(torch.float32).reshape(1).contiguous()
+        d_w = torch.empty_like(w)
+        ws = torch.empty(max(8, int(_loss_lib.lib().l4dl_los_workspace(N, T))), dtype=torch.uint8, device=w.device)
+        _loss_lib.call("l4dl_los_bwd", ops._p(w), ops._p(z), ops._p(d), int(d.dtype == torch.float16), N, T, ops._p(ctx.sched), ctx.step,
+                       ctx.iters, ops._p(gs), ops._p(d_w), ops._p(ws), ops._stream())
+        return d_w.view(ctx.shape), None, None, None, None, None
+
+
+def line_of_sight_loss(outputs, gt_depth, global_step, iters, sched=None):
+    """= urf_loss(outputs, gt_depth, global_step, iters), evaluated by the fused HIP path (``_LineOfSightLossFn``): five sweeps
+    over ``weights`` / ``z_vals`` for value and gradient together, no [N, T] temporary, no host read.
+    sched: FlatAdam's device schedule ([iterations so far, lr factor], fp32) or None.  When given, the tolerance follows
+    ``sched[0]`` as it stands on the device when the kernels run and ``global_step`` is ignored -- what lets the term be part of
+    a captured step.  gt_depth: fp32 or fp16 (``KITTI360Dataset`` preloads fp16 images); no gradient for it or for ``z_vals``."""
+    return _LineOfSightLossFn.apply(outputs["weights"], outputs["z_vals"], gt_depth, global_step, iters, sched)
+
+
 def _patch_grads(img, sobel):
     """img [n_patch, 1, px, py] -> (d/dx, d/dy): Sobel responses (same size) or forward differences (one shorter)."""
     if sobel:
@@ -740,6 +790,7 @@ class Trainer:
         # restatement of runner.py:179-220 (lidar_loss / ray_chamfer_loss; what the tests compare the fused nodes with)
         self.fused_losses = (depth_loss, raydrop_loss, intensity_loss) == ("l1", "mse", "mse") and bool(fused_losses)
         self.fused_flow_loss = bool(fused_losses)  # the scene-flow term as one autograd node (_SceneFlowLossFn)
+        self.fused_urf = bool(fused_losses)        # the line-of-sight term as one autograd node (_LineOfSightLossFn), any criteria
         self.graph_batch_inside = bool(graph_batch_inside)
         # flow_loss_stream: the scene-flow term (about 50 small launches on a frame's point clouds, none of which fills the chip) runs
         # on a stream of its own next to the render path's forward and backward (eager steps only; a captured step keeps one stream)
@@ -782,7 +833,11 @@ class Trainer:
                                           self.dataset.scale)
         if self.urf:  # a per-ray mean like the chamfer term
             gt = data["images_lidar"]
-            loss = loss + urf_loss(out, gt[:, :, 2] * gt[:, :, 0], self.opt.step_count, self.iters) / self.world
+            gt_depth = gt[:, :, 2] * gt[:, :, 0]
+            if getattr(self, "fused_urf", False) and out["weights"].is_cuda:  # tolerance from the device schedule when there is one
+                loss = loss + line_of_sight_loss(out, gt_depth, self.opt.step_count, self.iters, sched=self.opt.sched) / self.world
+            else:
+                loss = loss + urf_loss(out, gt_depth, self.opt.step_count, self.iters) / self.world
         return loss
 
     def _flow_term(self, data, t_ground=None):
@@ -805,8 +860,9 @@ class Trainer:
     def graphs_supported(self):
         """A step can be captured when nothing in it needs the host: single rank (the RCCL all-reduce is issued by torch's
         process group), a dataset that draws its batch on the device (``batch_for`` + ``register`` of its generator), no
-        patch / line-of-sight terms with host-side schedules."""
-        return (self.reducer is None and not self.urf and hasattr(self.dataset, "batch_for") and hasattr(self.dataset, "next_frame")
+        patch terms, and the line-of-sight term only as the fused node (``fused_urf``: its tolerance follows the optimiser's
+        schedule on the device; the torch restatement ``urf_loss`` computes it on the host from ``opt.step_count``)."""
+        return (self.reducer is None and (not self.urf or getattr(self, "fused_urf", False)) and hasattr(self.dataset, "batch_for") and hasattr(self.dataset, "next_frame")
                 and getattr(self.dataset, "patch_size_lidar", 1) == 1 and self.model._store.flat.is_cuda)
 
     def train_step_graphed(self, frame=None):
