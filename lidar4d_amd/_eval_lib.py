@@ -4,10 +4,9 @@ Same conventions as ``_lib`` (status -> HipExtensionError, ``*_workspace`` retur
 own that is loaded on FIRST USE, not at ``import lidar4d_amd``: a process that never evaluates a frame does not map it,
 and a missing liblidar4d_eval.so breaks nothing else.
 """
-import ctypes as C
 import os
 
-from ._lib import HipExtensionError, P, I32, F32
+from ._lib import Binding, HipExtensionError, P, I32, F32
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "liblidar4d_eval.so")
@@ -20,32 +19,5 @@ SIGNATURES = {
     "l4de_image_errors": [P, P, I32, I32, F32, F32, P, P, P],
 }
 
-_lib = None
-
-
-def lib():
-    """Load liblidar4d_eval.so (once).  Raises HipExtensionError if it has not been built."""
-    global _lib
-    if _lib is not None:
-        return _lib
-    if not os.path.exists(LIB_PATH):
-        raise HipExtensionError(
-            f"{LIB_PATH} not found: build the HIP extension first (python -c 'import __graft_entry__ as g; g.build()' "
-            "or make -C lidar4d_amd/csrc).  DepthMeter / IntensityMeter have no CPU fallback.")
-    l = C.CDLL(LIB_PATH)
-    l.l4de_version.restype = C.c_int
-    l.l4de_last_error.restype = C.c_char_p
-    if l.l4de_version() != ABI_VERSION:
-        raise HipExtensionError(f"ABI mismatch: library {l.l4de_version()} != binding {ABI_VERSION}; rebuild")
-    for name, args in SIGNATURES.items():
-        fn = getattr(l, name)
-        fn.argtypes = args
-        fn.restype = C.c_int64 if name.endswith("_workspace") else C.c_int
-    _lib = l
-    return l
-
-
-def call(name, *args):
-    status = getattr(lib(), name)(*args)
-    if status != 0:
-        raise HipExtensionError(f"{name} failed: {lib().l4de_last_error().decode()}")
+_binding = Binding(LIB_PATH, "l4de_", ABI_VERSION, SIGNATURES, "DepthMeter / IntensityMeter have no CPU fallback.")
+lib, version, call = _binding.lib, _binding.version, _binding.call

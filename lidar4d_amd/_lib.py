@@ -132,42 +132,53 @@ SIGNATURES = {
     "l4d_streams_mask": [],
 }
 
-_lib = None
-
 
 class HipExtensionError(RuntimeError):
     pass
 
 
-def lib():
-    """Load liblidar4d_hip.so (once).  Raises HipExtensionError if it has not been built."""
-    global _lib
-    if _lib is not None:
-        return _lib
-    if not os.path.exists(LIB_PATH):
-        raise HipExtensionError(
-            f"{LIB_PATH} not found: build the HIP extension first (python -c 'import __graft_entry__ as g; g.build()' "
-            "or make -C lidar4d_amd/csrc).  lidar4d_amd has no CPU fallback.")
-    l = C.CDLL(LIB_PATH)
-    l.l4d_version.restype = C.c_int
-    l.l4d_last_error.restype = C.c_char_p
-    if l.l4d_version() != ABI_VERSION:
-        raise HipExtensionError(f"ABI mismatch: library {l.l4d_version()} != binding {ABI_VERSION}; rebuild")
-    for name, args in SIGNATURES.items():
-        fn = getattr(l, name)
-        fn.argtypes = args
-        fn.restype = C.c_int64 if name.endswith("_workspace") else C.c_int
-    _lib = l
-    return l
+class Binding:
+    """One shared library behind one public header: mapped on the first ``lib()``, refused if its ``<prefix>version()`` is not the
+    binding's, every entry point of ``signatures`` typed (``*_workspace`` return int64, everything else an int status)."""
+
+    def __init__(self, path, prefix, abi_version, signatures, no_fallback):
+        self.path, self.prefix, self.abi_version, self.signatures, self.no_fallback = path, prefix, abi_version, signatures, no_fallback
+        self._lib = None
+
+    def lib(self):
+        """Load the library (once).  Raises HipExtensionError if it has not been built."""
+        if self._lib is not None:
+            return self._lib
+        if not os.path.exists(self.path):
+            raise HipExtensionError(
+                f"{self.path} not found: build the HIP extension first (python -c 'import __graft_entry__ as g; g.build()' "
+                f"or make -C lidar4d_amd/csrc).  {self.no_fallback}")
+        l = C.CDLL(self.path)
+        version = getattr(l, self.prefix + "version")
+        version.restype = C.c_int
+        getattr(l, self.prefix + "last_error").restype = C.c_char_p
+        if version() != self.abi_version:
+            raise HipExtensionError(f"ABI mismatch: library {version()} != binding {self.abi_version}; rebuild")
+        for name, args in self.signatures.items():
+            fn = getattr(l, name)
+            fn.argtypes = args
+            fn.restype = C.c_int64 if name.endswith("_workspace") else C.c_int
+        self._lib = l
+        return l
+
+    def version(self):
+        return getattr(self.lib(), self.prefix + "version")()
+
+    def check(self, status, name):
+        if status != 0:
+            raise HipExtensionError(f"{name} failed: {getattr(self.lib(), self.prefix + 'last_error')().decode()}")
+
+    def call(self, name, *args):
+        self.check(getattr(self.lib(), name)(*args), name)
 
 
-def check(status, name):
-    if status != 0:
-        raise HipExtensionError(f"{name} failed: {lib().l4d_last_error().decode()}")
-
-
-def call(name, *args):
-    check(getattr(lib(), name)(*args), name)
+_binding = Binding(LIB_PATH, "l4d_", ABI_VERSION, SIGNATURES, "lidar4d_amd has no CPU fallback.")
+lib, version, check, call = _binding.lib, _binding.version, _binding.check, _binding.call
 
 
 def profile_start():

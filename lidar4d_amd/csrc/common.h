@@ -23,6 +23,13 @@ L4D_INTERNAL void l4d_set_error(int code, const char* where);
     }                                                   \
   } while (0)
 
+// an entry point refuses its arguments: the text for <prefix>last_error(), status 1
+#define L4D_FAIL(msg)       \
+  do {                      \
+    l4d_set_error(1, msg);  \
+    return 1;               \
+  } while (0)
+
 // Every kernel launch of the library goes through this macro: when profiling is switched on (l4d_profile_enable, used by
 // bench.py's per-kernel pass) a pair of HIP events is recorded around the launch ON THE LAUNCH STREAM, so the durations
 // bench.py reports are per KERNEL (same names as rocprofv3's kernel trace), also for entry points that launch several.

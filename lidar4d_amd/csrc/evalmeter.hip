@@ -16,18 +16,14 @@
 // Every floating-point reduction has a fixed order (thread-strided sums, shuffle tree, waves in order; partials summed by one
 // workgroup); the only atomics are integer counters.  The same input gives the same bits.
 #include "common.h"
+#include "wave_dev.h"
 #include "../../include/lidar4d_eval.h"
 
 extern "C" int l4de_version(void) { return L4DE_ABI_VERSION; }
 extern "C" const char* l4de_last_error(void) { return l4d_last_error(); }
 
-#define EM_FAIL(msg)        \
-  do {                      \
-    l4d_set_error(1, msg);  \
-    return 1;               \
-  } while (0)
-
 #define EM_THREADS 256
+#define EM_WAVES (EM_THREADS / L4D_WAVE)
 #define EM_CHUNK 2048          // pixels per workgroup and grid-stride step of the streaming kernels
 #define EM_MAX_BLOCKS 1024     // ... whose grid, and so the number of partials, is bounded
 #define EM_MAX_PIXELS ((int64_t)1 << 28)
@@ -70,25 +66,14 @@ static inline bool eval_shape_ok(int32_t H, int32_t W) {
 // the reference's masked assignments (x[x < lo] = lo; x[x > hi] = hi): a NaN fails both comparisons and stays
 __device__ __forceinline__ float clamp_keep_nan(float x, float lo, float hi) { return x < lo ? lo : (x > hi ? hi : x); }
 
-// sum over the workgroup, the same order every time: shuffle tree inside a wave, then the waves in order.  sh: [EM_THREADS / 64]
-__device__ __forceinline__ double block_sum(double v, double* sh) {
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_down(v, o);
-  if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = v;
-  __syncthreads();
-  double s = sh[0];
-  for (int w = 1; w < EM_THREADS / 64; ++w) s += sh[w];
-  __syncthreads();
-  return s;
-}
-
 // ---- pass over the pixels: differences, partial sums, first histogram ---------------------------------------------------------------
 __global__ void __launch_bounds__(EM_THREADS) eval_errors_kernel(const float* __restrict__ pred, const float* __restrict__ gt, int n,
                                                                 float lo, float hi, uint32_t* __restrict__ absd,
                                                                 uint32_t* __restrict__ hist0, double* __restrict__ part_sq,
                                                                 float* __restrict__ part_min, float* __restrict__ part_max) {
   __shared__ uint32_t bins[256];
-  __shared__ double sh_sum[EM_THREADS / 64];
-  __shared__ float sh_min[EM_THREADS / 64], sh_max[EM_THREADS / 64];
+  __shared__ double sh_sum[EM_WAVES];
+  __shared__ float sh_min[EM_WAVES], sh_max[EM_WAVES];
   const int t = threadIdx.x;
   bins[t] = 0;
   __syncthreads();
@@ -109,21 +94,14 @@ __global__ void __launch_bounds__(EM_THREADS) eval_errors_kernel(const float* __
       atomicAdd(&bins[key >> 24], 1u);
     }
   }
-  for (int o = 32; o > 0; o >>= 1) {
-    const float a = __shfl_down(mn, o), b = __shfl_down(mx, o);
-    mn = a < mn ? a : mn;
-    mx = b > mx ? b : mx;
-  }
+  mn = wave_reduce(mn, RedMin());
+  mx = wave_reduce(mx, RedMax());
   if ((t & 63) == 0) { sh_min[t >> 6] = mn; sh_max[t >> 6] = mx; }
-  sq = block_sum(sq, sh_sum);  // (its barriers also cover sh_min / sh_max and bins)
+  sq = block_reduce<EM_WAVES>(sq, sh_sum, RedSum());  // (its barriers also cover sh_min / sh_max and bins)
   if (t == 0) {
-    for (int w = 1; w < EM_THREADS / 64; ++w) {
-      mn = sh_min[w] < mn ? sh_min[w] : mn;
-      mx = sh_max[w] > mx ? sh_max[w] : mx;
-    }
+    part_min[blockIdx.x] = waves_combine<EM_WAVES>(sh_min, RedMin());
+    part_max[blockIdx.x] = waves_combine<EM_WAVES>(sh_max, RedMax());
     part_sq[blockIdx.x] = sq;
-    part_min[blockIdx.x] = mn;
-    part_max[blockIdx.x] = mx;
   }
   if (bins[t]) atomicAdd(&hist0[t], bins[t]);
 }
@@ -193,8 +171,8 @@ __global__ void __launch_bounds__(EM_THREADS) eval_ssim_kernel(const float* __re
                                                               double* __restrict__ part_ssim) {
   __shared__ float sp[SS_IH][SS_IW], sg[SS_IH][SS_IW];
   __shared__ double rows[5][SS_IH][SS_TW];
-  __shared__ double sh_sum[EM_THREADS / 64];
-  __shared__ float sh_min[EM_THREADS / 64], sh_max[EM_THREADS / 64];
+  __shared__ double sh_sum[EM_WAVES];
+  __shared__ float sh_min[EM_WAVES], sh_max[EM_WAVES];
   const int t = threadIdx.x;
   const int y0 = (int)(blockIdx.x / tiles_x) * SS_TH, x0 = (int)(blockIdx.x % tiles_x) * SS_TW;
   // data range of the clamped ground truth from the first pass's partials
@@ -203,11 +181,8 @@ __global__ void __launch_bounds__(EM_THREADS) eval_ssim_kernel(const float* __re
     mn = part_min[i] < mn ? part_min[i] : mn;
     mx = part_max[i] > mx ? part_max[i] : mx;
   }
-  for (int o = 32; o > 0; o >>= 1) {
-    const float a = __shfl_down(mn, o), b = __shfl_down(mx, o);
-    mn = a < mn ? a : mn;
-    mx = b > mx ? b : mx;
-  }
+  mn = wave_reduce(mn, RedMin());
+  mx = wave_reduce(mx, RedMax());
   if ((t & 63) == 0) { sh_min[t >> 6] = mn; sh_max[t >> 6] = mx; }
   // the clamped tile and its apron; pixels beyond the image (ragged tiles) read as 0 and only feed windows that are not counted
   for (int i = t; i < SS_IH * SS_IW; i += EM_THREADS) {
@@ -218,11 +193,8 @@ __global__ void __launch_bounds__(EM_THREADS) eval_ssim_kernel(const float* __re
     sg[r][c] = in ? clamp_keep_nan(gt[at], lo, hi) : 0.0f;
   }
   __syncthreads();
-  mn = sh_min[0], mx = sh_max[0];
-  for (int w = 1; w < EM_THREADS / 64; ++w) {
-    mn = sh_min[w] < mn ? sh_min[w] : mn;
-    mx = sh_max[w] > mx ? sh_max[w] : mx;
-  }
+  mn = waves_combine<EM_WAVES>(sh_min, RedMin());
+  mx = waves_combine<EM_WAVES>(sh_max, RedMax());
   const double R = (double)mx - (double)mn;
   const double C1 = (0.01 * R) * (0.01 * R), C2 = (0.03 * R) * (0.03 * R);
   for (int i = t; i < SS_IH * SS_TW; i += EM_THREADS) {
@@ -263,7 +235,7 @@ __global__ void __launch_bounds__(EM_THREADS) eval_ssim_kernel(const float* __re
     const double vx = cov_norm * (s[2] - ux * ux), vy = cov_norm * (s[3] - uy * uy), vxy = cov_norm * (s[4] - ux * uy);
     acc += ((2.0 * ux * uy + C1) * (2.0 * vxy + C2)) / ((ux * ux + uy * uy + C1) * (vx + vy + C2));
   }
-  acc = block_sum(acc, sh_sum);
+  acc = block_reduce<EM_WAVES>(acc, sh_sum, RedSum());
   if (t == 0) part_ssim[blockIdx.x] = acc;
 }
 
@@ -271,14 +243,14 @@ __global__ void __launch_bounds__(EM_THREADS) eval_ssim_kernel(const float* __re
 __global__ void __launch_bounds__(EM_THREADS) eval_finalize_kernel(const uint32_t* __restrict__ hist, const double* __restrict__ part_sq,
                                                                   int n_part, const double* __restrict__ part_ssim, int n_tiles, int n,
                                                                   int H, int W, float hi, double* __restrict__ out) {
-  __shared__ double sh_sum[EM_THREADS / 64];
+  __shared__ double sh_sum[EM_WAVES];
   __shared__ uint32_t sh_key[2];
   const int t = threadIdx.x;
   double sq = 0.0, ss = 0.0;
   for (int i = t; i < n_part; i += EM_THREADS) sq += part_sq[i];
   for (int i = t; i < n_tiles; i += EM_THREADS) ss += part_ssim[i];
-  sq = block_sum(sq, sh_sum);
-  ss = block_sum(ss, sh_sum);
+  sq = block_reduce<EM_WAVES>(sq, sh_sum, RedSum());
+  ss = block_reduce<EM_WAVES>(ss, sh_sum, RedSum());
   if (t < 64) {
     uint32_t k0 = (uint32_t)(n - 1) >> 1, k1 = (uint32_t)n >> 1;
     const uint32_t a = select_prefix(hist, EM_PASSES, 0, k0), b = select_prefix(hist, EM_PASSES, 1, k1);
@@ -304,10 +276,10 @@ extern "C" int64_t l4de_image_errors_workspace(int32_t H, int32_t W) {
 extern "C" int l4de_image_errors(const float* pred, const float* gt, int32_t H, int32_t W, float lo, float hi, double* out,
                                  void* workspace, void* stream_) {
   hipStream_t stream = (hipStream_t)stream_;
-  if (H < SS_WIN || W < SS_WIN) EM_FAIL("l4de_image_errors: H and W must be at least 7 (one SSIM window)");
-  if (!eval_shape_ok(H, W)) EM_FAIL("l4de_image_errors: more than 2^28 pixels");
-  if (!pred || !gt || !out || !workspace) EM_FAIL("l4de_image_errors: null pointer");
-  if (((uintptr_t)workspace & 7) != 0) EM_FAIL("l4de_image_errors: workspace must be 8-byte aligned");
+  if (H < SS_WIN || W < SS_WIN) L4D_FAIL("l4de_image_errors: H and W must be at least 7 (one SSIM window)");
+  if (!eval_shape_ok(H, W)) L4D_FAIL("l4de_image_errors: more than 2^28 pixels");
+  if (!pred || !gt || !out || !workspace) L4D_FAIL("l4de_image_errors: null pointer");
+  if (((uintptr_t)workspace & 7) != 0) L4D_FAIL("l4de_image_errors: workspace must be 8-byte aligned");
   EvalWs ws;
   eval_ws_carve(workspace, H, W, &ws);
   const int n = H * W;

@@ -16,16 +16,11 @@
 #include <stdio.h>
 
 #include "common.h"
+#include "wave_dev.h"
 #include "../../include/lidar4d_loss.h"
 
 extern "C" int l4dl_version(void) { return L4DL_ABI_VERSION; }
 extern "C" const char* l4dl_last_error(void) { return l4d_last_error(); }
-
-#define LL_FAIL(msg)        \
-  do {                      \
-    l4d_set_error(1, msg);  \
-    return 1;               \
-  } while (0)
 
 #define LL_THREADS 256
 #define LL_WAVES (LL_THREADS / L4D_WAVE)  // rays a workgroup works on at a time: one per wavefront
@@ -119,26 +114,6 @@ __device__ __forceinline__ void los_store(float* __restrict__ p, const LosVec<V>
   }
 }
 
-// ---- reductions with a fixed order ---------------------------------------------------------------------------------------------------
-// sum over the workgroup: shuffle tree inside a wave, then the waves in order.  sh: [LL_WAVES]
-__device__ __forceinline__ double los_block_sum(double v, double* sh) {
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_down(v, o);
-  if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = v;
-  __syncthreads();
-  double s = sh[0];
-  for (int w = 1; w < LL_WAVES; ++w) s += sh[w];
-  __syncthreads();
-  return s;
-}
-__device__ __forceinline__ float los_block_max(float v, float* sh) {
-  for (int o = 32; o > 0; o >>= 1) v = fmaxf(v, __shfl_down(v, o));
-  if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = v;
-  __syncthreads();
-  float s = sh[0];
-  for (int w = 1; w < LL_WAVES; ++w) s = fmaxf(s, sh[w]);
-  __syncthreads();
-  return s;
-}
 // the pre-pass's partials -> normaliser and n_hit, in every thread of the workgroup
 __device__ __forceinline__ void los_pre_result(const float* __restrict__ part_max, const uint32_t* __restrict__ part_hit, int n_part,
                                                float& m, double& n_hit) {
@@ -150,8 +125,8 @@ __device__ __forceinline__ void los_pre_result(const float* __restrict__ part_ma
     mm = fmaxf(mm, part_max[i]);
     h += (double)part_hit[i];
   }
-  m = los_block_max(mm, sh_max);
-  n_hit = los_block_sum(h, sh_hit);
+  m = block_reduce<LL_WAVES>(mm, sh_max, RedFmax());
+  n_hit = block_reduce<LL_WAVES>(h, sh_hit, RedSum());
 }
 
 // ---- pre-pass: normaliser and n_hit -------------------------------------------------------------------------------------------------
@@ -189,8 +164,8 @@ __global__ void __launch_bounds__(LL_THREADS) los_pre_kernel(const float* __rest
       }
     }
   }
-  m = los_block_max(one ? 1.0f : m, sh_max);
-  const double h = los_block_sum((double)hits, sh_hit);
+  m = block_reduce<LL_WAVES>(one ? 1.0f : m, sh_max, RedFmax());
+  const double h = block_reduce<LL_WAVES>((double)hits, sh_hit, RedSum());
   if (threadIdx.x == 0) {
     part_max[blockIdx.x] = m;
     part_hit[blockIdx.x] = (uint32_t)h;
@@ -228,8 +203,8 @@ __global__ void __launch_bounds__(LL_THREADS) los_sums_kernel(const float* __res
       }
     }
   }
-  s_empty = los_block_sum(s_empty, sh_sum);
-  s_near = los_block_sum(s_near, sh_sum);
+  s_empty = block_reduce<LL_WAVES>(s_empty, sh_sum, RedSum());
+  s_near = block_reduce<LL_WAVES>(s_near, sh_sum, RedSum());
   if (threadIdx.x == 0) {
     part_empty[blockIdx.x] = s_empty;
     part_near[blockIdx.x] = s_near;
@@ -248,8 +223,8 @@ __global__ void __launch_bounds__(LL_THREADS) los_finish_kernel(const double* __
     s_empty += part_empty[i];
     s_near += part_near[i];
   }
-  s_empty = los_block_sum(s_empty, sh_sum);
-  s_near = los_block_sum(s_near, sh_sum);
+  s_empty = block_reduce<LL_WAVES>(s_empty, sh_sum, RedSum());
+  s_near = block_reduce<LL_WAVES>(s_near, sh_sum, RedSum());
   if (threadIdx.x == 0) loss_out[0] = (float)(0.1 * (s_empty / n_hit) + 0.1 * (s_near / n_hit));
 }
 
@@ -344,7 +319,7 @@ extern "C" int l4dl_los_bwd(const float* weights, const float* z_vals, const voi
                             void* stream_) {
   hipStream_t stream = (hipStream_t)stream_;
   if (los_check("l4dl_los_bwd", weights, z_vals, gt_depth, N, T, iters, d_weights, workspace)) return 1;
-  if (!g) LL_FAIL("l4dl_los_bwd: null pointer");
+  if (!g) L4D_FAIL("l4dl_los_bwd: null pointer");
   LosWs ws;
   los_ws_carve(workspace, &ws);
   const int blocks = los_blocks(N), half = gt_half != 0;

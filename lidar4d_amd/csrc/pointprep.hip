@@ -25,11 +25,6 @@
 extern "C" int l4dp_version(void) { return L4DP_ABI_VERSION; }
 extern "C" const char* l4dp_last_error(void) { return l4d_last_error(); }
 
-#define PP_FAIL(msg)        \
-  do {                      \
-    l4d_set_error(1, msg);  \
-    return 1;               \
-  } while (0)
 #define PP_MAX_POINTS ((int64_t)1 << 28)  // 32-bit indices and byte offsets throughout
 
 // ---- predicates + ordered compaction ---------------------------------------------------------------------------------------------
@@ -120,9 +115,9 @@ extern "C" int64_t l4dp_compact_workspace(int64_t n) { return (ceil_div64(n > 0 
 extern "C" int l4dp_range_filter(const float* points, int64_t n, float dist_min, float dist_max, float z_min, float z_max,
                                  float* out, int32_t* out_index, int32_t* count, void* workspace, void* stream_) {
   hipStream_t stream = (hipStream_t)stream_;
-  if (n < 0 || n > PP_MAX_POINTS || !count) PP_FAIL("l4dp_range_filter: bad n or null count");
+  if (n < 0 || n > PP_MAX_POINTS || !count) L4D_FAIL("l4dp_range_filter: bad n or null count");
   if (n == 0) { l4d_fill_async(count, 0u, 4, stream); return 0; }
-  if (!points || !out || !workspace) PP_FAIL("l4dp_range_filter: null pointer");
+  if (!points || !out || !workspace) L4D_FAIL("l4dp_range_filter: null pointer");
   RangePred pred{dist_min, dist_max, z_min, z_max};
   compact_launch(points, n, pred, out, out_index, count, workspace, stream);
   L4D_LAUNCH_CHECK("l4dp_range_filter");
@@ -312,10 +307,10 @@ extern "C" int64_t l4dp_knn_workspace(int64_t n) { return n > 0 ? (knn_pad(n) * 
 extern "C" int l4dp_knn_mean_dist(const float* points, int64_t n, int32_t k, const int32_t* order, float* avg, void* workspace,
                                   void* stream_) {
   hipStream_t stream = (hipStream_t)stream_;
-  if (n < 0 || n > PP_MAX_POINTS) PP_FAIL("l4dp_knn_mean_dist: bad n");
-  if (k < 1 || k > L4DP_MAX_NEIGHBORS) PP_FAIL("l4dp_knn_mean_dist: k must be in [1, 64]");
+  if (n < 0 || n > PP_MAX_POINTS) L4D_FAIL("l4dp_knn_mean_dist: bad n");
+  if (k < 1 || k > L4DP_MAX_NEIGHBORS) L4D_FAIL("l4dp_knn_mean_dist: k must be in [1, 64]");
   if (n == 0) return 0;
-  if (!points || !avg || !workspace) PP_FAIL("l4dp_knn_mean_dist: null pointer");
+  if (!points || !avg || !workspace) L4D_FAIL("l4dp_knn_mean_dist: null pointer");
   const int n_pad = (int)knn_pad(n), nb_pad = (int)knn_box_pad(n);
   const int k_eff = (int)(k < n ? k : n);
   float* soa = (float*)workspace;
@@ -331,7 +326,8 @@ extern "C" int l4dp_knn_mean_dist(const float* points, int64_t n, int32_t k, con
 // ---- outlier threshold -----------------------------------------------------------------------------------------------------------
 #define ST_THREADS 1024
 
-// sum over the workgroup in a fixed order (the same value in every thread)
+// sum over the workgroup in a fixed order (the same value in every thread).  Not wave_dev.h's block_reduce: the xor butterfly
+// needs no per-step lane select, which the down-tree pays for with six more registers in this kernel.
 __device__ __forceinline__ double block_sum_f64(double v, double* sh) {
   for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
   __syncthreads();  // (sh may still be read from the call before)
@@ -365,9 +361,9 @@ __global__ void __launch_bounds__(ST_THREADS) outlier_stats_kernel(const float* 
 extern "C" int l4dp_outlier_filter(const float* points, const float* avg, int64_t n, double std_ratio, float* out,
                                    int32_t* out_index, int32_t* count, double* stats, void* workspace, void* stream_) {
   hipStream_t stream = (hipStream_t)stream_;
-  if (n < 0 || n > PP_MAX_POINTS || !count) PP_FAIL("l4dp_outlier_filter: bad n or null count");
+  if (n < 0 || n > PP_MAX_POINTS || !count) L4D_FAIL("l4dp_outlier_filter: bad n or null count");
   if (n == 0) { l4d_fill_async(count, 0u, 4, stream); return 0; }
-  if (!points || !avg || !out || !stats || !workspace) PP_FAIL("l4dp_outlier_filter: null pointer");
+  if (!points || !avg || !out || !stats || !workspace) L4D_FAIL("l4dp_outlier_filter: null pointer");
   L4D_LAUNCH(outlier_stats_kernel, dim3(1), dim3(ST_THREADS), 0, stream, avg, n, std_ratio, stats);
   BelowPred pred{avg, stats};
   compact_launch(points, n, pred, out, out_index, count, workspace, stream);
@@ -455,9 +451,9 @@ __global__ void __launch_bounds__(PL_THREADS) plane_mask_kernel(const float* __r
 extern "C" int l4dp_plane_score(const float* points, int64_t n, const int32_t* triples, int32_t n_hyp, float y_gap, float threshold,
                                 int32_t* valid, float* coeffs, int32_t* counts, void* stream_) {
   hipStream_t stream = (hipStream_t)stream_;
-  if (n < 0 || n > PP_MAX_POINTS || n_hyp < 0) PP_FAIL("l4dp_plane_score: bad n or n_hyp");
+  if (n < 0 || n > PP_MAX_POINTS || n_hyp < 0) L4D_FAIL("l4dp_plane_score: bad n or n_hyp");
   if (n_hyp == 0) return 0;
-  if (!triples || !valid || !coeffs || !counts || (n > 0 && !points)) PP_FAIL("l4dp_plane_score: null pointer");
+  if (!triples || !valid || !coeffs || !counts || (n > 0 && !points)) L4D_FAIL("l4dp_plane_score: null pointer");
   L4D_LAUNCH(plane_fit_kernel, dim3((unsigned)ceil_div64(n_hyp, 64)), dim3(64), 0, stream, points, (int)n, triples, (int)n_hyp, y_gap,
              valid, coeffs, counts);
   if (n > 0)
@@ -470,9 +466,9 @@ extern "C" int l4dp_plane_score(const float* points, int64_t n, const int32_t* t
 extern "C" int l4dp_plane_mask(const float* points, int64_t n, const float* coeffs, int32_t n_planes, float threshold, uint8_t* mask,
                                void* stream_) {
   hipStream_t stream = (hipStream_t)stream_;
-  if (n < 0 || n > PP_MAX_POINTS || n_planes < 0) PP_FAIL("l4dp_plane_mask: bad n or n_planes");
+  if (n < 0 || n > PP_MAX_POINTS || n_planes < 0) L4D_FAIL("l4dp_plane_mask: bad n or n_planes");
   if (n == 0 || n_planes == 0) return 0;
-  if (!points || !coeffs || !mask) PP_FAIL("l4dp_plane_mask: null pointer");
+  if (!points || !coeffs || !mask) L4D_FAIL("l4dp_plane_mask: null pointer");
   L4D_LAUNCH(plane_mask_kernel, dim3((unsigned)ceil_div64(n, PL_THREADS)), dim3(PL_THREADS), 0, stream, points, (int)n, coeffs,
              (int)n_planes, threshold, mask);
   L4D_LAUNCH_CHECK("l4dp_plane_mask");

@@ -138,6 +138,48 @@ __device__ __forceinline__ void wave_scan(const WaveRuns& r, float v[K]) {
 #undef L4D_FMAC_BCAST
 }
 
+// ---- reductions over a workgroup with a fixed order ----------------------------------------------------------------------------
+// The combining operations, op(acc, x).  RedMin / RedMax are the compare-and-select forms: a NaN in x is passed over and a NaN in
+// acc stays (the evaluation meters' data range); RedFmax is fmaxf, which drops a NaN on either side.
+struct RedSum {
+  template <typename T> __device__ __forceinline__ T operator()(T acc, T x) const { return acc + x; }
+};
+struct RedMin {
+  template <typename T> __device__ __forceinline__ T operator()(T acc, T x) const { return x < acc ? x : acc; }
+};
+struct RedMax {
+  template <typename T> __device__ __forceinline__ T operator()(T acc, T x) const { return x > acc ? x : acc; }
+};
+struct RedFmax {
+  __device__ __forceinline__ float operator()(float acc, float x) const { return fmaxf(acc, x); }
+};
+// Shuffle-down tree, offsets 32 ... 1: LANE 0 ends up with the wave's result (the other lanes hold partial results).
+template <typename T, typename Op>
+__device__ __forceinline__ T wave_reduce(T v, Op op) {
+  for (int o = 32; o > 0; o >>= 1) v = op(v, __shfl_down(v, o));
+  return v;
+}
+// sh[0], sh[1], ... combined in ascending order, starting from sh[0]
+template <int WAVES, typename T, typename Op>
+__device__ __forceinline__ T waves_combine(const T* sh, Op op) {
+  T s = sh[0];
+  for (int w = 1; w < WAVES; ++w) s = op(s, sh[w]);
+  return s;
+}
+// The result over a workgroup of WAVES wavefronts, in every thread and with the same bits on every run: the tree above inside a
+// wave, lane 0 of each wave to sh[wave], barrier, the waves in index order, barrier (so sh may be reused at once).
+// Precondition: a one-dimensional workgroup of exactly WAVES * L4D_WAVE threads, all of which call it; sh holds WAVES values.
+// A kernel that reduces several values and wants to share the barriers uses the two steps above directly.
+template <int WAVES, typename T, typename Op>
+__device__ __forceinline__ T block_reduce(T v, T* sh, Op op) {
+  v = wave_reduce(v, op);
+  if (threadIdx.x % L4D_WAVE == 0) sh[threadIdx.x / L4D_WAVE] = v;
+  __syncthreads();
+  const T s = waves_combine<WAVES>(sh, op);
+  __syncthreads();
+  return s;
+}
+
 // running maximum of |v| that turns into +inf as soon as a non-finite value is seen (fmaxf alone drops nan): the
 // fixed-point statistics double as the "gradient overflowed" signal of the adjoint chain (common.h, f2h_grad)
 __device__ __forceinline__ float amax_nf(float m, float v) { return nonfinite(v) ? __builtin_inff() : fmaxf(m, fabsf(v)); }

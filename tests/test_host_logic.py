@@ -1,4 +1,4 @@
-"""CPU tests of the host-side logic: C-ABI library loads and exports every declared symbol (no compute calls),
+"""CPU tests of the host-side logic (the C ABI through the checks of tests/test_abi_cpu.py, no compute calls),
 grid geometry agrees with the oracle's, state-dict contract, flat parameter arenas, ray generation against the
 reference-generated fixture, the loud failure without a GPU."""
 import ctypes
@@ -9,32 +9,13 @@ import numpy as np
 import pytest
 import torch
 
+import test_abi_cpu as abi
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
 def test_library_exports_declared_abi():
-    from lidar4d_amd import _lib
-    header = open(os.path.join(ROOT, "include", "lidar4d_hip.h")).read()
-    declared = set(re.findall(r"\b(l4d_[a-z0-9_]+)\s*\(", header))
-    assert {"l4d_version", "l4d_last_error"} <= declared
-    if not os.path.exists(_lib.LIB_PATH):
-        pytest.skip("liblidar4d_hip.so not built (run __graft_entry__.build())")
-    lib = ctypes.CDLL(_lib.LIB_PATH)
-    for name in sorted(declared):
-        assert hasattr(lib, name), f"{name} declared in include/lidar4d_hip.h but not exported"
-    bound = set(_lib.SIGNATURES) | {"l4d_version", "l4d_last_error"}
-    assert declared == bound, (declared - bound, bound - declared)
-    assert _lib.lib().l4d_version() == _lib.ABI_VERSION
-    # ... and nothing else: the helpers the kernels' translation units share (error text, launch profiling) stay inside the
-    # shared object (four unlisted l4d_* exports)
-    import shutil
-    import subprocess
-    if shutil.which("nm"):
-        out = subprocess.run(["nm", "-D", "--defined-only", _lib.LIB_PATH], capture_output=True, text=True, check=True).stdout
-        exported = {l.split()[-1] for l in out.splitlines() if l.split()}
-        # (round 5: linked with csrc/exports.map -- kernel stubs, kernel handles and host-side C++ helpers are no longer in the
-        # dynamic symbol table either)
-        assert exported == declared, (sorted(exported - declared)[:8], declared - exported)
+    abi.check_exports_declared_abi(abi.HIP)
 
 
 def test_ctypes_structs_match_header_layout():
@@ -365,33 +346,7 @@ def test_checkpoint_roundtrip_and_reference_style_file(tmp_path):
 
 
 def test_ctypes_signatures_match_header_prototypes():
-    """Every prototype of include/lidar4d_hip.h against lidar4d_amd._lib.SIGNATURES: same number of arguments and the same
-    kind (pointer / int32 / int64 / float / double) in every position -- a drifted binding would pass garbage silently."""
-    from lidar4d_amd import _lib
-    header = open(os.path.join(ROOT, "include", "lidar4d_hip.h")).read()
-    header = re.sub(r"/\*.*?\*/", " ", header, flags=re.S)
-    protos = dict(re.findall(r"\b(?:int|int64_t|void\s*\*)\s*(l4d_[a-z0-9_]+)\s*\(([^;{]*?)\)\s*;", header, flags=re.S))
-
-    def kind(arg):
-        arg = arg.strip()
-        if "*" in arg:
-            return "ptr"
-        for name, k in (("int64_t", "i64"), ("int32_t", "i32"), ("double", "f64"), ("float", "f32"), ("int ", "i32")):
-            if arg.startswith(name):
-                return k
-        raise AssertionError(f"unparsed argument {arg!r}")
-
-    ckind = {_lib.P: "ptr", _lib.I32: "i32", _lib.I64: "i64", _lib.F32: "f32", _lib.F64: "f64", _lib.GD: "ptr", _lib.FD: "ptr",
-             _lib.FG: "ptr", _lib.PI32: "ptr", _lib.PI64: "ptr", _lib.PP: "ptr"}
-    checked = 0
-    for name, argtypes in _lib.SIGNATURES.items():
-        assert name in protos, f"{name} bound but no prototype found"
-        args = [a for a in protos[name].split(",") if a.strip() and a.strip() != "void"]
-        want = [kind(a) for a in args]
-        got = [ckind[t] for t in argtypes]
-        assert want == got, (name, want, got)
-        checked += 1
-    assert checked == len(_lib.SIGNATURES) >= 36
+    abi.check_ctypes_signatures_match_header_prototypes(abi.HIP)
 
 
 def test_shift_trajectory_matches_reference_script():
@@ -491,21 +446,7 @@ def test_refine_unet_loop_learns_and_follows_reference_recipe():
 
 
 def test_c_abi_from_plain_c(tmp_path):
-    """tests/c_abi/abi_check.c: include/lidar4d_hip.h consumed by a C99 compiler (-Wall -Wextra -Werror), every declared
-    entry point linked against the shared library, version / error calls executed -- no Python, no torch in the boundary."""
-    import shutil
-    import subprocess
-    from lidar4d_amd import _lib
-    if shutil.which("gcc") is None or not os.path.exists(_lib.LIB_PATH):
-        pytest.skip("needs gcc and the built library")
-    exe = str(tmp_path / "abi_check")
-    libdir = os.path.dirname(_lib.LIB_PATH)
-    subprocess.run(["gcc", "-std=c99", "-Wall", "-Wextra", "-Werror", "-I", os.path.join(ROOT, "include"),
-                    os.path.join(ROOT, "tests", "c_abi", "abi_check.c"), "-L", libdir, "-llidar4d_hip", f"-Wl,-rpath,{libdir}",
-                    "-o", exe], check=True)
-    out = subprocess.run([exe], check=True, capture_output=True, text=True).stdout
-    n_declared = len(_lib.SIGNATURES) + 2
-    assert out.startswith(f"{n_declared} entry points, ABI v{_lib.ABI_VERSION}")
+    abi.check_c_abi_from_plain_c(abi.HIP, tmp_path)
 
 
 def test_frame_index_is_the_fp32_product_of_the_reference():

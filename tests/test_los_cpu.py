@@ -1,94 +1,27 @@
 """CPU tests of the fused line-of-sight loss (lidar4d_amd.trainer.line_of_sight_loss, include/lidar4d_loss.h): the fourth shared
-object's ABI, its loading on first use, the absence of a CPU path, and that a Trainer without ``fused_urf`` keeps the torch
-route (tests/test_gpu_los.py compares the kernels with it)."""
-import ctypes
-import os
-import re
-import shutil
-import subprocess
-import sys
-
+object's ABI and its loading on first use (the checks of tests/test_abi_cpu.py), its argument checks, the absence of a CPU path, and that a
+Trainer without ``fused_urf`` keeps the torch route (tests/test_gpu_los.py compares the kernels with it)."""
 import pytest
 import torch
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-HEADER = os.path.join(ROOT, "include", "lidar4d_loss.h")
+import test_abi_cpu as abi
 
 
-def _declared():
-    header = open(HEADER).read()
-    return set(re.findall(r"\b(l4dl_[a-z0-9_]+)\s*\(", re.sub(r"/\*.*?\*/", " ", header, flags=re.S)))
-
-
-def _exported(path):
-    out = subprocess.run(["nm", "-D", "--defined-only", path], capture_output=True, text=True, check=True).stdout
-    return {l.split()[-1] for l in out.splitlines() if l.split()}
-
-
+# ---- the fourth shared object (the checks: tests/test_abi_cpu.py) ---------------------------------------------------------------
 def test_loss_library_exports_declared_abi():
-    from lidar4d_amd import _eval_lib, _lib, _loss_lib, _prep_lib
-    declared = _declared()
-    assert declared == set(_loss_lib.SIGNATURES) | {"l4dl_version", "l4dl_last_error"}
-    assert set(_loss_lib.SIGNATURES) == {"l4dl_los_workspace", "l4dl_los_fwd", "l4dl_los_bwd"}
-    assert os.path.exists(_loss_lib.LIB_PATH), "liblidar4d_loss.so not built (run __graft_entry__.build())"
-    lib = ctypes.CDLL(_loss_lib.LIB_PATH)
-    for name in sorted(declared):
-        assert hasattr(lib, name), f"{name} declared in include/lidar4d_loss.h but not exported"
-    assert _loss_lib.lib().l4dl_version() == _loss_lib.ABI_VERSION == 1
-    assert shutil.which("nm"), "needs binutils nm"
-    exported = _exported(_loss_lib.LIB_PATH)
-    assert exported == declared, (sorted(exported - declared)[:8], declared - exported)
-    # ... and the other three libraries gained nothing
-    for other in (_lib.LIB_PATH, _prep_lib.LIB_PATH, _eval_lib.LIB_PATH):
-        assert not [s for s in _exported(other) if "l4dl_" in s], other
+    abi.check_exports_declared_abi(abi.LOSS)
 
 
 def test_loss_ctypes_signatures_match_header_prototypes():
-    """Every prototype of include/lidar4d_loss.h against _loss_lib.SIGNATURES: same number of arguments and the same kind
-    (pointer / int32 / int64 / float / double) in every position."""
-    from lidar4d_amd import _lib, _loss_lib
-    header = re.sub(r"/\*.*?\*/", " ", open(HEADER).read(), flags=re.S)
-    protos = dict(re.findall(r"\b(?:int|int64_t|void\s*\*)\s*(l4dl_[a-z0-9_]+)\s*\(([^;{]*?)\)\s*;", header, flags=re.S))
-
-    def kind(arg):
-        arg = arg.strip()
-        if "*" in arg:
-            return "ptr"
-        for name, k in (("int64_t", "i64"), ("int32_t", "i32"), ("double", "f64"), ("float", "f32"), ("int ", "i32")):
-            if arg.startswith(name):
-                return k
-        raise AssertionError(f"unparsed argument {arg!r}")
-
-    ckind = {_lib.P: "ptr", _lib.I32: "i32", _lib.I64: "i64", _lib.F32: "f32", _lib.F64: "f64"}
-    for name, argtypes in _loss_lib.SIGNATURES.items():
-        assert name in protos, f"{name} bound but no prototype found"
-        args = [a for a in protos[name].split(",") if a.strip() and a.strip() != "void"]
-        assert [kind(a) for a in args] == [ckind[t] for t in argtypes], name
-        if not name.endswith("_workspace"):
-            assert re.match(r"void\s*\*\s*stream$", args[-1].strip()), name  # the stream comes last
-    assert set(protos) == set(_loss_lib.SIGNATURES) | {"l4dl_version"}  # (l4dl_last_error returns const char*)
+    abi.check_ctypes_signatures_match_header_prototypes(abi.LOSS)
 
 
 def test_loss_c_abi_from_plain_c(tmp_path):
-    from lidar4d_amd import _loss_lib
-    assert shutil.which("gcc") and os.path.exists(_loss_lib.LIB_PATH), "needs gcc and the built library"
-    exe = str(tmp_path / "loss_abi_check")
-    libdir = os.path.dirname(_loss_lib.LIB_PATH)
-    subprocess.run(["gcc", "-std=c99", "-Wall", "-Wextra", "-Werror", "-I", os.path.join(ROOT, "include"),
-                    os.path.join(ROOT, "tests", "c_abi", "loss_abi_check.c"), "-L", libdir, "-llidar4d_loss", f"-Wl,-rpath,{libdir}",
-                    "-o", exe], check=True)
-    out = subprocess.run([exe], check=True, capture_output=True, text=True).stdout
-    assert out.startswith(f"{len(_loss_lib.SIGNATURES) + 2} entry points, ABI v{_loss_lib.ABI_VERSION}")
+    abi.check_c_abi_from_plain_c(abi.LOSS, tmp_path)
 
 
 def test_loss_library_is_loaded_on_first_use_only():
-    code = ("import lidar4d_amd, lidar4d_amd.trainer\n"
-            "from lidar4d_amd import _loss_lib\n"
-            "assert callable(lidar4d_amd.trainer.line_of_sight_loss)\n"
-            "assert 'liblidar4d_loss' not in open('/proc/self/maps').read()\n"
-            "_loss_lib.lib()\n"
-            "assert 'liblidar4d_loss' in open('/proc/self/maps').read()\n")
-    subprocess.run([sys.executable, "-c", code], check=True, cwd=ROOT)
+    abi.check_loaded_on_first_use_only(abi.LOSS)
 
 
 def test_workspace_and_argument_checks_need_no_device():

@@ -1,98 +1,30 @@
 """CPU tests of the evaluation meters (lidar4d_amd/metrics.py DepthMeter / IntensityMeter, include/lidar4d_eval.h): the third
-shared object's ABI, the absence of a CPU path, and the numpy restatements tests/test_gpu_meters.py compares the kernels with
-(tests/meters_ref.py): the float64 formula against plain loops and against the reference's own float32 arithmetic."""
-import ctypes
-import os
-import re
-import shutil
-import subprocess
-import sys
-
+shared object's ABI (the checks of tests/test_abi_cpu.py) and argument checks, the absence of a CPU path, and the numpy restatements
+tests/test_gpu_meters.py compares the kernels with (tests/meters_ref.py): the float64 formula against plain loops and against the
+reference's own float32 arithmetic."""
 import numpy as np
 import pytest
 import torch
 
 import meters_ref as ref
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-HEADER = os.path.join(ROOT, "include", "lidar4d_eval.h")
+import test_abi_cpu as abi
 
 
-# ---- the third shared object -------------------------------------------------------------------------------------------------
-def _declared():
-    header = open(HEADER).read()
-    return set(re.findall(r"\b(l4de_[a-z0-9_]+)\s*\(", re.sub(r"/\*.*?\*/", " ", header, flags=re.S)))
-
-
-def _exported(path):
-    out = subprocess.run(["nm", "-D", "--defined-only", path], capture_output=True, text=True, check=True).stdout
-    return {l.split()[-1] for l in out.splitlines() if l.split()}
-
-
+# ---- the third shared object (the checks: tests/test_abi_cpu.py) ---------------------------------------------------------------
 def test_eval_library_exports_declared_abi():
-    from lidar4d_amd import _eval_lib, _lib, _prep_lib
-    declared = _declared()
-    assert {"l4de_version", "l4de_last_error"} <= declared
-    assert declared == set(_eval_lib.SIGNATURES) | {"l4de_version", "l4de_last_error"}
-    assert os.path.exists(_eval_lib.LIB_PATH), "liblidar4d_eval.so not built (run __graft_entry__.build())"
-    lib = ctypes.CDLL(_eval_lib.LIB_PATH)
-    for name in sorted(declared):
-        assert hasattr(lib, name), f"{name} declared in include/lidar4d_eval.h but not exported"
-    assert _eval_lib.lib().l4de_version() == _eval_lib.ABI_VERSION == 1
-    assert shutil.which("nm"), "needs binutils nm"
-    exported = _exported(_eval_lib.LIB_PATH)
-    assert exported == declared, (sorted(exported - declared)[:8], declared - exported)
-    # ... and the render and point-preparation libraries gained nothing
-    for other in (_lib.LIB_PATH, _prep_lib.LIB_PATH):
-        assert not [s for s in _exported(other) if "l4de_" in s], other
+    abi.check_exports_declared_abi(abi.EVAL)
 
 
 def test_eval_ctypes_signatures_match_header_prototypes():
-    """Every prototype of include/lidar4d_eval.h against _eval_lib.SIGNATURES: same number of arguments and the same kind
-    (pointer / int32 / int64 / float / double) in every position."""
-    from lidar4d_amd import _eval_lib, _lib
-    header = re.sub(r"/\*.*?\*/", " ", open(HEADER).read(), flags=re.S)
-    protos = dict(re.findall(r"\b(?:int|int64_t|void\s*\*)\s*(l4de_[a-z0-9_]+)\s*\(([^;{]*?)\)\s*;", header, flags=re.S))
-
-    def kind(arg):
-        arg = arg.strip()
-        if "*" in arg:
-            return "ptr"
-        for name, k in (("int64_t", "i64"), ("int32_t", "i32"), ("double", "f64"), ("float", "f32"), ("int ", "i32")):
-            if arg.startswith(name):
-                return k
-        raise AssertionError(f"unparsed argument {arg!r}")
-
-    ckind = {_lib.P: "ptr", _lib.I32: "i32", _lib.I64: "i64", _lib.F32: "f32", _lib.F64: "f64"}
-    for name, argtypes in _eval_lib.SIGNATURES.items():
-        assert name in protos, f"{name} bound but no prototype found"
-        args = [a for a in protos[name].split(",") if a.strip() and a.strip() != "void"]
-        assert [kind(a) for a in args] == [ckind[t] for t in argtypes], name
-    assert set(protos) == set(_eval_lib.SIGNATURES) | {"l4de_version"}  # (l4de_last_error returns const char*)
+    abi.check_ctypes_signatures_match_header_prototypes(abi.EVAL)
 
 
 def test_eval_c_abi_from_plain_c(tmp_path):
-    from lidar4d_amd import _eval_lib
-    assert shutil.which("gcc") and os.path.exists(_eval_lib.LIB_PATH), "needs gcc and the built library"
-    exe = str(tmp_path / "eval_abi_check")
-    libdir = os.path.dirname(_eval_lib.LIB_PATH)
-    subprocess.run(["gcc", "-std=c99", "-Wall", "-Wextra", "-Werror", "-I", os.path.join(ROOT, "include"),
-                    os.path.join(ROOT, "tests", "c_abi", "eval_abi_check.c"), "-L", libdir, "-llidar4d_eval", f"-Wl,-rpath,{libdir}",
-                    "-o", exe], check=True)
-    out = subprocess.run([exe], check=True, capture_output=True, text=True).stdout
-    assert out.startswith(f"{len(_eval_lib.SIGNATURES) + 2} entry points, ABI v{_eval_lib.ABI_VERSION}")
+    abi.check_c_abi_from_plain_c(abi.EVAL, tmp_path)
 
 
 def test_eval_library_is_loaded_on_first_use_only():
-    code = ("import lidar4d_amd, lidar4d_amd.trainer, lidar4d_amd.metrics\n"
-            "from lidar4d_amd import _eval_lib\n"
-            "from lidar4d_amd.metrics import DepthMeter, IntensityMeter\n"
-            "DepthMeter(1.0), IntensityMeter(1.0)\n"
-            "assert hasattr(lidar4d_amd.trainer.Trainer, 'evaluate')\n"
-            "assert 'liblidar4d_eval' not in open('/proc/self/maps').read()\n"
-            "_eval_lib.lib()\n"
-            "assert 'liblidar4d_eval' in open('/proc/self/maps').read()\n")
-    subprocess.run([sys.executable, "-c", code], check=True, cwd=ROOT)
+    abi.check_loaded_on_first_use_only(abi.EVAL)
 
 
 def test_workspace_and_argument_checks_need_no_device():

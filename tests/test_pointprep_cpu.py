@@ -1,23 +1,18 @@
 """CPU tests of the point-cloud preparation (lidar4d_amd/pointprep.py, include/lidar4d_prep.h): the numpy restatement
 (tests/pointprep_ref.py) against the fixture the reference's own functions wrote, the product's host-side RANSAC replay against
-the same fixture (stream consumption and the K logic, without a GPU), the second shared object's ABI, and the unchanged default
-of process_pointcloud."""
-import ctypes
+the same fixture (stream consumption and the K logic, without a GPU), the second shared object's ABI (the checks of
+tests/test_abi_cpu.py), and the unchanged default of process_pointcloud."""
 import os
 import random
-import re
-import shutil
-import subprocess
-import sys
 
 import numpy as np
 import pytest
 import torch
 
 import pointprep_ref as ref
+import test_abi_cpu as abi
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-HEADER = os.path.join(ROOT, "include", "lidar4d_prep.h")
 
 
 @pytest.fixture(scope="module")
@@ -109,78 +104,21 @@ def test_fixture_cloud_has_no_point_at_the_outlier_threshold(fx):
     assert np.count_nonzero(np.abs(avg - thr) <= 1e-4 * thr) <= 1
 
 
-# ---- the second shared object ------------------------------------------------------------------------------------------------
-def _declared():
-    header = open(HEADER).read()
-    return set(re.findall(r"\b(l4dp_[a-z0-9_]+)\s*\(", re.sub(r"/\*.*?\*/", " ", header, flags=re.S)))
-
-
+# ---- the second shared object (the checks: tests/test_abi_cpu.py) ---------------------------------------------------------------
 def test_prep_library_exports_declared_abi():
-    from lidar4d_amd import _lib, _prep_lib
-    declared = _declared()
-    assert {"l4dp_version", "l4dp_last_error"} <= declared
-    assert declared == set(_prep_lib.SIGNATURES) | {"l4dp_version", "l4dp_last_error"}
-    assert os.path.exists(_prep_lib.LIB_PATH), "liblidar4d_prep.so not built (run __graft_entry__.build())"
-    lib = ctypes.CDLL(_prep_lib.LIB_PATH)
-    for name in sorted(declared):
-        assert hasattr(lib, name), f"{name} declared in include/lidar4d_prep.h but not exported"
-    assert _prep_lib.lib().l4dp_version() == _prep_lib.ABI_VERSION
-    assert shutil.which("nm"), "needs binutils nm"
-    for path, want in ((_prep_lib.LIB_PATH, declared), ):
-        out = subprocess.run(["nm", "-D", "--defined-only", path], capture_output=True, text=True, check=True).stdout
-        exported = {l.split()[-1] for l in out.splitlines() if l.split()}
-        assert exported == want, (sorted(exported - want)[:8], want - exported)
-    # ... and the render library gained nothing
-    out = subprocess.run(["nm", "-D", "--defined-only", _lib.LIB_PATH], capture_output=True, text=True, check=True).stdout
-    assert not [l for l in out.splitlines() if "l4dp_" in l]
+    abi.check_exports_declared_abi(abi.PREP)
 
 
 def test_prep_ctypes_signatures_match_header_prototypes():
-    """Every prototype of include/lidar4d_prep.h against _prep_lib.SIGNATURES: same number of arguments and the same kind
-    (pointer / int32 / int64 / float / double) in every position."""
-    from lidar4d_amd import _lib, _prep_lib
-    header = re.sub(r"/\*.*?\*/", " ", open(HEADER).read(), flags=re.S)
-    protos = dict(re.findall(r"\b(?:int|int64_t|void\s*\*)\s*(l4dp_[a-z0-9_]+)\s*\(([^;{]*?)\)\s*;", header, flags=re.S))
-
-    def kind(arg):
-        arg = arg.strip()
-        if "*" in arg:
-            return "ptr"
-        for name, k in (("int64_t", "i64"), ("int32_t", "i32"), ("double", "f64"), ("float", "f32"), ("int ", "i32")):
-            if arg.startswith(name):
-                return k
-        raise AssertionError(f"unparsed argument {arg!r}")
-
-    ckind = {_lib.P: "ptr", _lib.I32: "i32", _lib.I64: "i64", _lib.F32: "f32", _lib.F64: "f64"}
-    for name, argtypes in _prep_lib.SIGNATURES.items():
-        assert name in protos, f"{name} bound but no prototype found"
-        args = [a for a in protos[name].split(",") if a.strip() and a.strip() != "void"]
-        assert [kind(a) for a in args] == [ckind[t] for t in argtypes], name
-    assert set(protos) == set(_prep_lib.SIGNATURES) | {"l4dp_version"}  # (l4dp_last_error returns const char*)
+    abi.check_ctypes_signatures_match_header_prototypes(abi.PREP)
 
 
 def test_prep_c_abi_from_plain_c(tmp_path):
-    from lidar4d_amd import _prep_lib
-    assert shutil.which("gcc") and os.path.exists(_prep_lib.LIB_PATH), "needs gcc and the built library"
-    exe = str(tmp_path / "prep_abi_check")
-    libdir = os.path.dirname(_prep_lib.LIB_PATH)
-    subprocess.run(["gcc", "-std=c99", "-Wall", "-Wextra", "-Werror", "-I", os.path.join(ROOT, "include"),
-                    os.path.join(ROOT, "tests", "c_abi", "prep_abi_check.c"), "-L", libdir, "-llidar4d_prep", f"-Wl,-rpath,{libdir}",
-                    "-o", exe], check=True)
-    out = subprocess.run([exe], check=True, capture_output=True, text=True).stdout
-    assert out.startswith(f"{len(_prep_lib.SIGNATURES) + 2} entry points, ABI v{_prep_lib.ABI_VERSION}")
+    abi.check_c_abi_from_plain_c(abi.PREP, tmp_path)
 
 
 def test_prep_library_is_loaded_on_first_use_only():
-    code = ("import lidar4d_amd, lidar4d_amd.trainer, sys\n"
-            "assert 'lidar4d_amd.pointprep' not in sys.modules and 'lidar4d_amd._prep_lib' not in sys.modules\n"
-            "from lidar4d_amd import pointprep, _prep_lib\n"
-            "assert 'pointprep' not in lidar4d_amd.__all__\n"
-            "maps = open('/proc/self/maps').read()\n"
-            "assert 'liblidar4d_prep' not in maps\n"
-            "_prep_lib.lib()\n"
-            "assert 'liblidar4d_prep' in open('/proc/self/maps').read()\n")
-    subprocess.run([sys.executable, "-c", code], check=True, cwd=ROOT)
+    abi.check_loaded_on_first_use_only(abi.PREP)
 
 
 def test_pointprep_has_no_cpu_fallback(fx):
