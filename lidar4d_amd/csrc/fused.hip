@@ -466,15 +466,20 @@ __global__ void __launch_bounds__(256) warp_coords_kernel(const float* __restric
   for (int k = 0; k < 6; ++k) flowT[(int64_t)k * P + p] = fh[k];
 }
 
-__global__ void __launch_bounds__(DH_THREADS) dynhash_fwd_lds_kernel(FieldDesc fd, const float* __restrict__ xs,
-                                                                    const half_t* __restrict__ flowT,
-                                                                    const float* __restrict__ tinfo, int64_t P, int64_t chunk,
-                                                                    half_t* __restrict__ hdT) {
+// The body of both LDS kernels: one task = (plane in {xz, yz}, level lvl) over one chunk of samples.
+// HS 0: the dynamic stacks alone.  HS 1 / 2: the task ALSO evaluates the static 3-D grid's level lvl for half of its samples into the
+// level-major columns hsT[level][P][4] (what hashgrid.hip's hashgrid_fwd_levels_kernel writes; 2: with its x-neighbour pair loads).
+// The static gathers wait on the per-CU address path that this kernel leaves idle, while its other wavefronts hash and read LDS: the
+// two kernels run back to back otherwise, each stalled on the part of the CU the other does not use.  Every loop iteration takes two
+// samples: the xz task looks up the first one's static level, the yz task the second one's (a chunk's odd tail has no second sample,
+// and its first is the xz task's): every (sample, level) column is written exactly once.  Same device function, same fp32 coordinate
+// values (xs holds xt's) as the pre-pass: bit-identical columns.
+template <int HS>
+__device__ __forceinline__ void dynhash_fwd_lds_body(const FieldDesc& fd, const float* __restrict__ xs, const half_t* __restrict__ flowT,
+                                                     const float* __restrict__ tinfo, int64_t P, int64_t chunk,
+                                                     half_t* __restrict__ hdT, half_t* __restrict__ hsT, const int plane, const int lvl) {
   extern __shared__ uint4 lds_tab[];  // [entry] = {slice i1: 4 halfs, slice i2: 4 halfs}: both slices of a corner in ONE ds_read_b128
-  // task = (plane in {xz, yz}, level); hdT column = levels(xy) + ...
-  int task = blockIdx.y, plane = 1;
-  if (task >= fd.hd[1].n_levels) { task -= fd.hd[1].n_levels; plane = 2; }
-  const int lvl = task;
+  // hdT column = levels(xy) + ...
   const int col = fd.hd[0].n_levels + (plane == 2 ? fd.hd[1].n_levels : 0) + lvl;
   const int ca = plane == 2 ? 1 : 0, cb = 2;
   const GridDesc& g = fd.hd[plane];
@@ -559,6 +564,25 @@ __global__ void __launch_bounds__(DH_THREADS) dynhash_fwd_lds_kernel(FieldDesc f
       xb[e] = b + h2f(flowT[(int64_t)((e - 1) * 3 + cb) * P + p]);
     }
   };
+  // static grid, level lvl of sample ps (HS only: the fallback kernel reads nothing of the static grid).  No load under a lane's
+  // condition (it would be waited for where it is issued): a tail lane of the yz task repeats the first sample's lookup and drops
+  // the result.  The gathers are issued behind both samples' coordinate loads and consumed at once, ahead of the LDS part: what hides
+  // them is the other wavefronts of the CU (held across eval() they take some 20 registers more than a 1024-thread workgroup has:
+  // 96 - 128 bytes of scratch per lane in every form compiled)
+  auto hs_level = [&](int64_t ps, bool store, float xo, float xa, float xb) {
+    if constexpr (HS != 0) {
+      const float x3[3] = {plane == 2 ? xo : xa, plane == 2 ? xa : xo, xb};
+      float a[4];
+      level_lookup<3, 4, HS == 2>(fd.hs_table + (size_t)fd.hs.offset[lvl] * 4, fd.hs.scale[lvl], fd.hs.res[lvl], fd.hs.size[lvl],
+                                  (fd.hs.hashed_mask >> lvl) & 1u, x3, a);
+      half4_t h;
+#pragma unroll
+      for (int f = 0; f < 4; ++f) h[f] = f2h(a[f]);
+      typedef uint32_t u32x2_nt __attribute__((ext_vector_type(2)));
+      if (store) __builtin_nontemporal_store(__builtin_bit_cast(u32x2_nt, h), reinterpret_cast<u32x2_nt*>(hsT + ((int64_t)lvl * P + ps) * 4));
+    }
+  };
+  const float* xo_p = xs + (int64_t)(plane == 2 ? 0 : 1) * P;  // the static sample's third coordinate (the task's own: x or y, and z)
   auto walk = [&](auto fast_tag) {
     for (int64_t p0 = lo_p + threadIdx.x; p0 < hi_p; p0 += 2 * DH_THREADS) {
       const int64_t p1 = p0 + DH_THREADS;
@@ -567,12 +591,37 @@ __global__ void __launch_bounds__(DH_THREADS) dynhash_fwd_lds_kernel(FieldDesc f
       float xa0[3], xb0[3], xa1[3], xb1[3];
       load(p0, xa0, xb0);
       load(q1, xa1, xb1);
+      if constexpr (HS != 0) {
+        const int64_t ps = plane == 2 ? q1 : p0;
+        hs_level(ps, plane != 2 || ok1, xo_p[ps], plane == 2 ? xa1[0] : xa0[0], plane == 2 ? xb1[0] : xb0[0]);
+      }
       out[p0] = eval(fast_tag, xa0, xb0);
       if (ok1) out[p1] = eval(fast_tag, xa1, xb1);
     }
   };
   if (fast_level) walk(std::true_type{});
   else walk(std::false_type{});
+}
+
+// task = blockIdx.y, plane-major: the xz levels, then the yz levels
+__global__ void __launch_bounds__(DH_THREADS) dynhash_fwd_lds_kernel(FieldDesc fd, const float* __restrict__ xs,
+                                                                    const half_t* __restrict__ flowT,
+                                                                    const float* __restrict__ tinfo, int64_t P, int64_t chunk,
+                                                                    half_t* __restrict__ hdT) {
+  int task = blockIdx.y, plane = 1;
+  if (task >= fd.hd[1].n_levels) { task -= fd.hd[1].n_levels; plane = 2; }
+  dynhash_fwd_lds_body<0>(fd, xs, flowT, tinfo, P, chunk, hdT, nullptr, plane, task);
+}
+
+// ... with the static grid's level of the same number (all three grids have as many levels).  Tasks level-major -- blockIdx.y =
+// 2 * level + (plane - 1) -- so that the workgroups in flight at any moment gather from ONE static level's table and every L2 holds
+// that one (what ORDER 1 of hashgrid_fwd_levels_kernel is for): at one workgroup per CU the chip runs one or two tasks at a time.
+template <bool PAIRLD>
+__global__ void __launch_bounds__(DH_THREADS) dynhash_hs_fwd_lds_kernel(FieldDesc fd, const float* __restrict__ xs,
+                                                                       const half_t* __restrict__ flowT,
+                                                                       const float* __restrict__ tinfo, int64_t P, int64_t chunk,
+                                                                       half_t* __restrict__ hdT, half_t* __restrict__ hsT) {
+  dynhash_fwd_lds_body<PAIRLD ? 2 : 1>(fd, xs, flowT, tinfo, P, chunk, hdT, hsT, 1 + (int)(blockIdx.y & 1u), (int)(blockIdx.y >> 1));
 }
 
 // ---- sampling that also emits the normalised (x, t) rows the field kernels read --------------------
@@ -673,6 +722,13 @@ static int enc_hs_split() {
   return v;
 }
 
+// static grid's levels inside the LDS kernel's tasks (default; L4D_DH_HS_FUSED=0: the level-major pre-pass as a launch of its own, A/B)
+static int dh_hs_fused() {
+  static int v = -1;
+  if (v < 0) { const char* e = getenv("L4D_DH_HS_FUSED"); v = (e && e[0] == '0') ? 0 : 1; }
+  return v;
+}
+
 extern "C" int64_t l4d_plane_rows_workspace(const l4d_field_desc* f) {
   int64_t n = 0;
   for (int s = 0; s < f->n_scales; ++s)
@@ -702,6 +758,9 @@ static int encode_fwd_impl(const l4d_field_desc* f, const float* xt, const void*
   hipStream_t main_s = (hipStream_t)stream;
   // static grid: level-major pre-pass into the workspace (needs the workspace, the time-plane rows, F = 4 and enough points)
   const bool hs_pre = hd_scratch && plane_rows && enc_hs_split() && f->hash_static.n_features == 4 && P >= ENC_HS_PRE_MIN_POINTS;
+  // ... inside the LDS kernel's tasks where the three grids pair up level by level, as a launch of its own behind it otherwise
+  const bool dh_hs = hs_pre && dh_hs_fused() && d.hs.n_levels == d.hd[1].n_levels && d.hs.n_levels == d.hd[2].n_levels;
+  half_t* hsT = hs_pre ? (half_t*)((char*)hd_scratch + enc_ws_hs_offset(f, P)) : nullptr;
   if (hd_scratch) {
     if (d.hd[1].size[d.hd[1].n_levels - 1] > DH_MAX_ENTRIES || d.hd[2].size[d.hd[2].n_levels - 1] > DH_MAX_ENTRIES) {
       l4d_set_error(1, "l4d_density_encode_fwd: xz/yz slice tables exceed the LDS staging size; pass hd_scratch = null");
@@ -710,16 +769,23 @@ static int encode_fwd_impl(const l4d_field_desc* f, const float* xt, const void*
     int n_chunks = (int)std::min<int64_t>(256, std::max<int64_t>(1, ceil_div64(P, 8192)));
     const int64_t chunk = ceil_div64(P, n_chunks);
     n_chunks = (int)ceil_div64(P, chunk);
-    (void)hipFuncSetAttribute((const void*)dynhash_fwd_lds_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 2 * DH_MAX_ENTRIES * 8);
     const int64_t n_dyn = d.hd[0].n_levels + d.hd[1].n_levels + d.hd[2].n_levels;
     float* xs = (float*)((char*)hd_scratch + (n_dyn * P * 2 + 255) / 256 * 256);
     half_t* flowT = (half_t*)((char*)xs + (3 * P * 4 + 255) / 256 * 256);
     L4D_LAUNCH(warp_coords_kernel, dim3((unsigned)ceil_div64(P, 256)), dim3(256), 0, main_s, xt, (const half_t*)flow16, P, xs, flowT);
-    L4D_LAUNCH(dynhash_fwd_lds_kernel, dim3(n_chunks, d.hd[1].n_levels + d.hd[2].n_levels), dim3(DH_THREADS),
-               2 * DH_MAX_ENTRIES * 8, main_s, d, xs, flowT, tinfo, P, chunk, (half_t*)hd_scratch);
+    const dim3 dgrid(n_chunks, d.hd[1].n_levels + d.hd[2].n_levels);
+    const int dh_lds = 2 * DH_MAX_ENTRIES * 8;
+#define DH_LAUNCH(kernel, ...)                                                                                   \
+  do {                                                                                                           \
+    (void)hipFuncSetAttribute((const void*)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, dh_lds);          \
+    L4D_LAUNCH(kernel, dgrid, dim3(DH_THREADS), dh_lds, main_s, d, xs, flowT, tinfo, P, chunk, __VA_ARGS__);      \
+  } while (0)
+    if (dh_hs && l4d_hs_pair_ok(&d.hs, f->hash_static.n_features, d.hs_table)) DH_LAUNCH(dynhash_hs_fwd_lds_kernel<true>, (half_t*)hd_scratch, hsT);
+    else if (dh_hs) DH_LAUNCH(dynhash_hs_fwd_lds_kernel<false>, (half_t*)hd_scratch, hsT);
+    else DH_LAUNCH(dynhash_fwd_lds_kernel, (half_t*)hd_scratch);
+#undef DH_LAUNCH
   }
-  half_t* hsT = hs_pre ? (half_t*)((char*)hd_scratch + enc_ws_hs_offset(f, P)) : nullptr;
-  if (hs_pre) {
+  if (hs_pre && !dh_hs) {
     const int cols3[3] = {0, 1, 2};
     if (l4d_hashgrid_levels_launch(&d.hs, 3, 4, xt, P, 4, cols3, d.hs_table, hsT, main_s)) return 1;
   }

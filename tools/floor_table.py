@@ -52,7 +52,7 @@ LDS_ATOMICS = {"bin_reduce_kernel<3, 4": (8 * 4 * 2 * 4, LDS_U64),   # 8 levels 
                "bin_pass1_kernel<3, 4": (8 * 4, LDS_U32), "bin_pass1_kernel<3, 2": (7 * 4, LDS_U32)}  # ranks (returning)
 # wavefronts per SIMD where no kernel-trace summary is given (registers / LDS / workgroup size of the default build)
 OCCUPANCY = {"density_encode_fwd_kernel": 2, "planes_dyn_lds_kernel": 3, "mlp_bwd_kernel<6": 1, "mlp_bwd_kernel<8": 1, "mlp_bwd_kernel<1": 2,
-             "dynhash_fwd_lds_kernel": 4, "bin_pass1_kernel": 4, "bin_reduce_kernel": 8, "hashgrid_fwd_levels_kernel": 8,
+             "dynhash_fwd_lds_kernel": 4, "dynhash_hs_fwd_lds_kernel": 4, "bin_pass1_kernel": 4, "bin_reduce_kernel": 8, "hashgrid_fwd_levels_kernel": 8,
              "planes_static_lds_kernel": 8, "hashgrid_t_fwd_levels_kernel": 6, "dynhash_lds_kernel": 4, "mlp_fwd_kernel": 4}
 
 
