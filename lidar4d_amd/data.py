@@ -158,14 +158,23 @@ class SyntheticKitti360:
         pose = self.poses[frame:frame + 1]
         t = self.times[frame]
         # (num_rays <= 0 = "every pixel of the frame" in get_lidar_rays, kitti360_dataset.py:150-180: that case takes the torch path)
-        if (self.fused_batch and self.num_rays > 0 and torch.device(self.device).type == "cuda" and self.patch_size_lidar == 1
-                and not self.sort_pixels):
+        patch = self.patch_size_lidar
+        px, py = (patch, patch) if isinstance(patch, int) else ((patch[0], patch[0]) if len(patch) == 1 else tuple(patch))
+        if self.fused_batch and self.num_rays > 0 and torch.device(self.device).type == "cuda" and px > 0 and not self.sort_pixels:
             # the two draws of get_lidar_rays (same generator consumption), then ONE launch for pixel index, direction,
             # rotation, origin and the ground-truth gather (csrc/glue.hip: 33 torch launches otherwise)
             from . import ops
             n = min(self.num_rays, self.H * self.W)
-            top = torch.randint(0, self.H - 1, size=[n], device=self.device, generator=self.gen)
-            left = torch.randint(0, self.W, size=[n], device=self.device, generator=self.gen)
+            n_patch = n // (px * py)
+            if n_patch * px * py != n:
+                raise ValueError(f"SyntheticKitti360.batch_for: num_rays = {n} is not a multiple of the patch size {px} x {py}")
+            top = torch.randint(0, self.H - px, size=[n_patch], device=self.device, generator=self.gen)
+            left = torch.randint(0, self.W, size=[n_patch], device=self.device, generator=self.gen)
+            if px * py > 1:  # a patch's pixels: rows top + 0 .. px - 1, columns left + 0 .. py - 1 around the panorama, patch-row major
+                dr = torch.arange(px, device=self.device).repeat_interleave(py)
+                dc = torch.arange(py, device=self.device).repeat(px)
+                top = (top[:, None] + dr[None, :]).reshape(-1)
+                left = ((left[:, None] + dc[None, :]) % self.W).reshape(-1)
             rays_o, rays_d, images, _ = ops.lidar_ray_batch(top, left, self.poses[frame], self.fov, self.H, self.W, self.images[frame])
             return {"rays_o_lidar": rays_o, "rays_d_lidar": rays_d, "time": t, "images_lidar": images,
                     "poses_lidar": pose, "H_lidar": self.H, "W_lidar": self.W, "index": [frame],

@@ -233,6 +233,86 @@ def depth_grad_loss(pred_depth, gt_depth, gt_raydrop, patch_size, scale, alpha_g
     return loss
 
 
+def _patch_shape(patch_size):
+    """(px, py) of the reference's ``patch_size_lidar``: an int, [p] or [px, py]."""
+    if isinstance(patch_size, int):
+        return patch_size, patch_size
+    return (int(patch_size[0]), int(patch_size[0])) if len(patch_size) == 1 else (int(patch_size[0]), int(patch_size[1]))
+
+
+class _PatchGradLossFn(torch.autograd.Function):
+    """``depth_grad_loss`` as one autograd node on csrc/patchgrad.hip (liblidar4d_patch.so, include/lidar4d_patch.h): forward =
+    l4dg_patch_fwd (two launches), which also leaves the gradient wrt the predicted depths; backward = l4dg_patch_bwd, one launch
+    that scales it by the upstream gradient (the loss scale, a device scalar) -- the pattern of ``_PrimaryLossFn``.  Nothing in
+    the node needs the host, so a patch step can be captured."""
+
+    @staticmethod
+    def forward(ctx, pred, gt, hit, px, py, scale, kind, flags, alpha_grad, alpha_grad_norm, alpha_spatial, alpha_tv):
+        from . import _patch_lib
+        n = pred.numel()
+        p = pred.detach().to(torch.float32).reshape(n).contiguous()
+        half = gt.dtype == torch.float16
+        dt = torch.float16 if half else torch.float32
+        q, h = gt.detach().to(dt).reshape(n).contiguous(), hit.detach().to(dt).reshape(n).contiguous()
+        n_patch = n // (px * py)
+        loss = torch.empty(1, dtype=torch.float32, device=p.device)
+        g_pred = torch.empty_like(p)
+        ws = torch.empty(max(8, int(_patch_lib.lib().l4dg_patch_workspace(n_patch, px, py))), dtype=torch.uint8, device=p.device)
+        _patch_lib.call("l4dg_patch_fwd", ops._p(p), ops._p(q), ops._p(h), int(half), n_patch, px, py, float(scale), kind, flags,
+                        float(alpha_grad), float(alpha_grad_norm), float(alpha_spatial), float(alpha_tv), ops._p(loss), ops._p(g_pred),
+                        ops._p(ws), ops._stream())
+        ctx.save_for_backward(g_pred)
+        ctx.shape = pred.shape
+        return loss.reshape(())
+
+    @staticmethod
+    def backward(ctx, g):
+        from . import _patch_lib
+        (g_pred,) = ctx.saved_tensors
+        gs = g.detach().to(torch.float32).reshape(1).contiguous()
+        d_pred = torch.empty_like(g_pred)
+        _patch_lib.call("l4dg_patch_bwd", ops._p(g_pred), ops._p(gs), g_pred.numel(), ops._p(d_pred), ops._stream())
+        return (d_pred.view(ctx.shape),) + (None,) * 11
+
+
+def patch_depth_grad_loss(pred_depth, gt_depth, gt_raydrop, patch_size, scale, alpha_grad=0.1, kind="l1", sobel_grad=False,
+                          grad_loss=True, grad_norm_smooth=False, spatial_smooth=False, tv_loss=False, alpha_grad_norm=0.1,
+                          alpha_spatial=0.1, alpha_tv=0.1):
+    """= depth_grad_loss(...) with the same arguments, evaluated by the fused HIP path (``_PatchGradLossFn``): one sweep over the
+    patches for value and gradient together, three launches per step instead of about eighty, no host read.
+    gt_depth / gt_raydrop: fp32, or both fp16 (``KITTI360Dataset`` preloads fp16 images; forward differences only -- the
+    restatement's convolution refuses mixed dtypes, so there is nothing a Sobel result could be compared with).  No gradient
+    for them.  Patches of 2 x 2 up to 1024 pixels."""
+    from . import _patch_lib
+    px, py = _patch_shape(patch_size)
+    if px <= 1:
+        return pred_depth.new_zeros(())
+    for t, name in ((pred_depth, "pred_depth"), (gt_depth, "gt_depth"), (gt_raydrop, "gt_raydrop")):
+        if not t.is_cuda:  # (slices of the batch arrive strided: the node makes its own dense copies)
+            raise _patch_lib.HipExtensionError(f"patch_depth_grad_loss: {name} is on {t.device}: no CPU fallback "
+                                               "(trainer.depth_grad_loss is the torch restatement)")
+    if kind not in _patch_lib.KINDS:
+        raise ValueError(f"patch_depth_grad_loss: unknown kind {kind!r} (l1, mse, huber, cos)")
+    n = pred_depth.numel()
+    if py < 2 or px * py > _patch_lib.MAX_PATCH_PIXELS:
+        raise ValueError(f"patch_depth_grad_loss: patch {px} x {py}: both sides at least 2 and at most "
+                         f"{_patch_lib.MAX_PATCH_PIXELS} pixels")
+    if n == 0 or n % (px * py) != 0:
+        raise ValueError(f"patch_depth_grad_loss: {n} rays are not a whole number of {px} x {py} patches")
+    if gt_depth.numel() != n or gt_raydrop.numel() != n:
+        raise ValueError(f"patch_depth_grad_loss: {gt_depth.numel()} depths / {gt_raydrop.numel()} ray-drop values for {n} rays")
+    half = gt_depth.dtype == torch.float16 or gt_raydrop.dtype == torch.float16
+    if half and sobel_grad:
+        raise ValueError("patch_depth_grad_loss: sobel_grad with fp16 ground truth is not supported (forward differences only)")
+    if half:
+        gt_depth, gt_raydrop = gt_depth.to(torch.float16), gt_raydrop.to(torch.float16)
+    flags = (_patch_lib.SOBEL * bool(sobel_grad) + _patch_lib.GRAD_LOSS * bool(grad_loss)
+             + _patch_lib.GRAD_NORM_SMOOTH * bool(grad_norm_smooth) + _patch_lib.SPATIAL_SMOOTH * bool(spatial_smooth)
+             + _patch_lib.TV_LOSS * bool(tv_loss))
+    return _PatchGradLossFn.apply(pred_depth, gt_depth, gt_raydrop, px, py, scale, _patch_lib.KINDS[kind], flags, alpha_grad,
+                                  alpha_grad_norm, alpha_spatial, alpha_tv)
+
+
 def process_pointcloud(dataset, ground_split=None, removal=None):
     """runner.py:923-951 on the device: per frame, ground-truth range image -> points (lidar4d_amd.convert) -> split into
     non-ground / ground -> scene units and world frame.  Returns (pc_list, pc_ground_list), dicts keyed by str(frame).
@@ -773,7 +853,10 @@ class Trainer:
     def __init__(self, model, dataset, lr=1e-2, iters=30000, num_steps=768, chamfer=True, flow=True, urf=False,
                  ema_decay=None, loss_scaler=True, init_scale=65536.0, depth_loss="l1", raydrop_loss="mse",
                  intensity_loss="mse", epoch_steps=None, fused_losses=True, force_allreduce=False, overlap_allreduce=True,
-                 grad_transport="fp32", graph_batch_inside=True, flow_loss_stream=True, point_removal=None):
+                 grad_transport="fp32", graph_batch_inside=True, flow_loss_stream=True, point_removal=None,
+                 depth_grad_loss="l1", sobel_grad=False, grad_loss=True, grad_norm_smooth=False, spatial_smooth=False,
+                 tv_loss=False, alpha_grad=0.1, alpha_grad_norm=0.1, alpha_spatial=0.1, alpha_tv=0.1, fused_patch=None,
+                 change_patch_size_lidar=None, change_patch_size_epoch=2):
         """Defaults follow the reference's default run: the ray chamfer term is always part of its step
         (runner.py:215-220) and ``--flow_loss`` defaults to True (main_lidar4d.py:67).
         chamfer: a mean over the rank's own rays, so under data parallelism it is scaled by 1/world before the SUM
@@ -782,7 +865,14 @@ class Trainer:
         (DynamicLossScaler).  ema_decay: parameter EMA, updated once per epoch like the reference's (runner.py:534-535);
         an epoch = ``epoch_steps`` steps (default: one per training frame, the reference's loader length).
         point_removal: ``removal`` of process_pointcloud for the scene-flow clouds (``lidar4d_amd.pointprep.point_removal`` on a
-        real sequence); None keeps the synthetic scene's ground split."""
+        real sequence); None keeps the synthetic scene's ground split.
+        depth_grad_loss ... alpha_tv: the switches and weights of the patch depth-gradient terms (main_lidar4d.py:68-83), which
+        enter the loss whenever ``dataset.patch_size_lidar`` is not 1; fused_patch (default: ``fused_losses``): evaluate them as
+        one autograd node (``patch_depth_grad_loss``) instead of the torch restatement.
+        change_patch_size_lidar / change_patch_size_epoch: the reference's patch epochs (runner.py:694-705).  None (default)
+        leaves ``dataset.patch_size_lidar`` alone; a patch size such as [2, 8] -- the reference's default -- is set on the
+        dataset before the batch of every step of an epoch with ``epoch % change_patch_size_epoch == 0`` (epochs count from 1),
+        and 1 in the other epochs."""
         self.model, self.dataset, self.num_steps, self.chamfer = model, dataset, num_steps, chamfer
         self.flow, self.urf, self.iters = flow, urf, iters
         self.loss_kinds = dict(depth_loss=depth_loss, raydrop_loss=raydrop_loss, intensity_loss=intensity_loss)
@@ -791,6 +881,20 @@ class Trainer:
         self.fused_losses = (depth_loss, raydrop_loss, intensity_loss) == ("l1", "mse", "mse") and bool(fused_losses)
         self.fused_flow_loss = bool(fused_losses)  # the scene-flow term as one autograd node (_SceneFlowLossFn)
         self.fused_urf = bool(fused_losses)        # the line-of-sight term as one autograd node (_LineOfSightLossFn), any criteria
+        self.fused_patch = bool(fused_losses) if fused_patch is None else bool(fused_patch)  # the patch terms as one node (_PatchGradLossFn)
+        if depth_grad_loss not in ("l1", "mse", "huber", "cos"):
+            raise ValueError(f"Trainer: unknown depth_grad_loss {depth_grad_loss!r} (l1, mse, huber, cos)")
+        self.depth_grad_loss, self.sobel_grad, self.grad_loss = depth_grad_loss, bool(sobel_grad), bool(grad_loss)
+        self.grad_norm_smooth, self.spatial_smooth, self.tv_loss = bool(grad_norm_smooth), bool(spatial_smooth), bool(tv_loss)
+        self.alpha_grad, self.alpha_grad_norm, self.alpha_spatial, self.alpha_tv = alpha_grad, alpha_grad_norm, alpha_spatial, alpha_tv
+        self.change_patch_size_lidar, self.change_patch_size_epoch = change_patch_size_lidar, int(change_patch_size_epoch)
+        if change_patch_size_lidar is not None:
+            px, py = _patch_shape(change_patch_size_lidar)
+            rays = getattr(dataset, "num_rays", 0)
+            if px < 1 or py < 1 or rays <= 0 or rays % (px * py) != 0:
+                raise ValueError(f"Trainer: num_rays = {rays} is not a whole number of {px} x {py} patches (change_patch_size_lidar)")
+            if self.change_patch_size_epoch < 1:
+                raise ValueError("Trainer: change_patch_size_epoch must be at least 1")
         self.graph_batch_inside = bool(graph_batch_inside)
         # flow_loss_stream: the scene-flow term (about 50 small launches on a frame's point clouds, none of which fills the chip) runs
         # on a stream of its own next to the render path's forward and backward (eager steps only; a captured step keeps one stream)
@@ -829,8 +933,14 @@ class Trainer:
         patch = getattr(self.dataset, "patch_size_lidar", 1)
         if patch != 1:  # rays were drawn as pixel patches (runner.py:277-367); a sum over this rank's patches
             gt = data["images_lidar"]
-            loss = loss + depth_grad_loss(out["depth_lidar"] * gt[:, :, 0], gt[:, :, 2] * gt[:, :, 0], gt[:, :, 0], patch,
-                                          self.dataset.scale)
+            opt = lambda name, default: getattr(self, name, default)  # (a bare Trainer object: today's defaults, the torch route)
+            term = patch_depth_grad_loss if opt("fused_patch", False) and out["depth_lidar"].is_cuda else depth_grad_loss
+            loss = loss + term(out["depth_lidar"] * gt[:, :, 0], gt[:, :, 2] * gt[:, :, 0], gt[:, :, 0], patch, self.dataset.scale,
+                               alpha_grad=opt("alpha_grad", 0.1), kind=opt("depth_grad_loss", "l1"), sobel_grad=opt("sobel_grad", False),
+                               grad_loss=opt("grad_loss", True), grad_norm_smooth=opt("grad_norm_smooth", False),
+                               spatial_smooth=opt("spatial_smooth", False), tv_loss=opt("tv_loss", False),
+                               alpha_grad_norm=opt("alpha_grad_norm", 0.1), alpha_spatial=opt("alpha_spatial", 0.1),
+                               alpha_tv=opt("alpha_tv", 0.1))
         if self.urf:  # a per-ray mean like the chamfer term
             gt = data["images_lidar"]
             gt_depth = gt[:, :, 2] * gt[:, :, 0]
@@ -845,7 +955,17 @@ class Trainer:
         return flow_loss(self.model, self.pc_list, self.pc_ground_list, data["time"], self.dataset.num_frames, frame_idx=known,
                          fused=self.fused_flow_loss, t_ground=t_ground)
 
+    def _set_patch_epoch(self):
+        """runner.py:697-705: with ``change_patch_size_lidar`` the loader draws patches in every ``change_patch_size_epoch``-th
+        epoch and single pixels in the others; called before a step's batch is drawn.  -> the dataset's patch size."""
+        change = getattr(self, "change_patch_size_lidar", None)
+        if change is not None:
+            epoch = self.local_step // self.epoch_steps + 1
+            self.dataset.patch_size_lidar = change if epoch % self.change_patch_size_epoch == 0 else 1
+        return getattr(self.dataset, "patch_size_lidar", 1)
+
     def train_step(self, data=None):
+        self._set_patch_epoch()
         data = data if data is not None else self.dataset.batch()
         loss = self._step_device_work(data)
         self._step_host_bookkeeping()
@@ -859,19 +979,23 @@ class Trainer:
     # -- the same step as ONE hipGraph per frame -------------------------------------------------------------------------
     def graphs_supported(self):
         """A step can be captured when nothing in it needs the host: single rank (the RCCL all-reduce is issued by torch's
-        process group), a dataset that draws its batch on the device (``batch_for`` + ``register`` of its generator), no
-        patch terms, and the line-of-sight term only as the fused node (``fused_urf``: its tolerance follows the optimiser's
-        schedule on the device; the torch restatement ``urf_loss`` computes it on the host from ``opt.step_count``)."""
+        process group), a dataset that draws its batch on the device (``batch_for`` + ``register`` of its generator), the
+        patch terms and the line-of-sight term only as their fused nodes (``fused_patch``; ``fused_urf``: its tolerance follows
+        the optimiser's schedule on the device, the torch restatement ``urf_loss`` computes it on the host from
+        ``opt.step_count``)."""
+        patches = getattr(self.dataset, "patch_size_lidar", 1) != 1 or getattr(self, "change_patch_size_lidar", None) is not None
         return (self.reducer is None and (not self.urf or getattr(self, "fused_urf", False)) and hasattr(self.dataset, "batch_for") and hasattr(self.dataset, "next_frame")
-                and getattr(self.dataset, "patch_size_lidar", 1) == 1 and self.model._store.flat.is_cuda)
+                and (not patches or getattr(self, "fused_patch", False)) and self.model._store.flat.is_cuda)
 
     def train_step_graphed(self, frame=None):
-        """train_step as the replay of a hipGraph captured per frame index (the scene-flow loss walks that frame's point clouds, so
-        the launch sequence depends on the frame and on nothing else): batch draw (device RNG), forward, losses, backward,
+        """train_step as the replay of a hipGraph captured per frame index and patch size (the scene-flow loss walks that frame's
+        point clouds, and a patch epoch draws its batch differently and adds the patch terms: the launch sequence depends on the
+        two and on nothing else): batch draw (device RNG), forward, losses, backward,
         GradScaler check / skip / update, Adam with the learning-rate schedule on the device -- about 640 launches per step
         become one.  The first call for a frame runs one eager step (refreshes every host-side cache) and captures the next."""
         if not self.graphs_supported():
             raise RuntimeError("Trainer.train_step_graphed: this configuration needs the host inside a step (see graphs_supported)")
+        patch = self._set_patch_epoch()
         if frame is None:
             frame = self.dataset.next_frame()
         st = self.__dict__.setdefault("_step_graphs", {"pool": None, "graphs": {}})
@@ -879,7 +1003,8 @@ class Trainer:
         # graph_batch_inside=False: the batch is drawn by eager launches into static buffers before every replay (debugging aid,
         # tests/test_gpu_optim.py; default: the draw is part of the graph, the dataset's device generator is registered with it)
         outside = not self.graph_batch_inside
-        rec = st["graphs"].get(frame)
+        key = (frame, tuple(patch) if isinstance(patch, (list, tuple)) else patch)
+        rec = st["graphs"].get(key)
         if rec is None:
             static = None
             if outside:
@@ -903,7 +1028,7 @@ class Trainer:
                 loss_g = self._step_device_work(draw()).detach()
             if st["pool"] is None:
                 st["pool"] = graph.pool()
-            st["graphs"][frame] = {"graph": graph, "loss": loss_g, "static": static}
+            st["graphs"][key] = {"graph": graph, "loss": loss_g, "static": static}
             self._step_host_bookkeeping()
             return loss
         if rec["static"] is not None:
