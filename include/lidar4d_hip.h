@@ -160,6 +160,8 @@ int l4d_mlp_fwd_sigma(const void* x, int64_t P, int32_t in_pad, int32_t n_hidden
  * act: the forward's saved activations, or null = recompute them from x inside the kernel (saves 128 B/row/layer of HBM
  * traffic twice; built for in_pad <= 32 with 1-3 hidden layers and for the 128 -> 64 -> 16 density network, where it is the
  * default of the fused path since round 5: -0.17 ms per step; other shapes would spill registers and return an error).
+ * A non-null act must be what l4d_mlp_fwd stored, that is non-negative, with +0 (bit pattern 0x0000) for dead units: the
+ * ReLU gate opens on any non-zero bit pattern, so a -0 or a negative value there would let gradient through a dead unit.
  * dx_absmax: null, or a device fp32 that receives (atomic max; zero it first) the largest |dx| of the input columns
  * [absmax_col_lo, absmax_col_hi) (multiples of 16) as the kernel stores them, +inf if one of them is not finite -- the
  * consumer of those columns then needs no pass of its own to scale its fixed-point accumulators (l4d_density_encode_bwd). */

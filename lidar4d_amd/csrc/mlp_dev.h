@@ -54,8 +54,8 @@ __device__ __forceinline__ h8 relu_pack(const f4& lo, const f4& hi) {
   // Convert first, then ONE packed fp16 maximum per pair (v_cvt_pk_f16_f32 + v_pk_max_f16: half the instructions of eight
   // v_max_f32 + four conversions; same values: rounding is monotone and keeps zero).  Measured over the step's MLP kernels:
   // -0.30 ms (gpurun_out/r4j).  The integer form (max of the bit patterns as int16) made the compiler split the conversions
-  // again and lost most of that (r4k).  A result of -0 (from a tiny negative input) is possible here; every consumer compares
-  // "> 0" as a float, for which it is a zero.
+  // again and lost most of that (r4k).  A tiny negative input converts to -0, and the maximum with +0 gives +0 (v_pk_max_f16 orders
+  // -0 below +0): the result never carries a sign bit, which relu_gate relies on (tests/test_gpu_mlp_exact.py, the gate at +-0).
   typedef _Float16 h2 __attribute__((ext_vector_type(2)));
   const h2 z = {(half_t)0.0f, (half_t)0.0f};
 #pragma unroll
