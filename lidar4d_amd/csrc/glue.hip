@@ -17,6 +17,7 @@
 #include <algorithm>
 
 #include "common.h"
+#include "glue_dev.h"
 
 // ---- ray batch -------------------------------------------------------------------------------------------------------------
 __global__ void __launch_bounds__(256) lidar_ray_batch_kernel(const int64_t* __restrict__ rows, const int64_t* __restrict__ cols, int n,
@@ -71,31 +72,6 @@ __device__ __forceinline__ float block_sum_1024(float v, float* red /* [1024] */
   const float r = red[0];
   __syncthreads();
   return r;
-}
-
-// fixed-order sum of one value per thread over a 256-thread workgroup
-__device__ __forceinline__ float block_sum_256(float v, float* red /* [256] */) {
-  red[threadIdx.x] = v;
-  __syncthreads();
-#pragma unroll
-  for (int s = 128; s > 0; s >>= 1) {
-    if ((int)threadIdx.x < s) red[threadIdx.x] += red[threadIdx.x + s];
-    __syncthreads();
-  }
-  const float r = red[0];
-  __syncthreads();
-  return r;
-}
-
-// loss[0] = (accumulate ? loss[0] : 0) + coef * (partial[0] + partial[1] + ...), summed in index order by one workgroup: the
-// per-block partial sums of the kernels below become ONE number that is the same every run (no floating-point atomics)
-__global__ void __launch_bounds__(256) sum_partials_kernel(const float* __restrict__ partial, int n, float coef, int accumulate,
-                                                           float* __restrict__ loss) {
-  __shared__ float red[256];
-  float acc = 0.0f;
-  for (int i = threadIdx.x; i < n; i += 256) acc += partial[i];
-  const float total = block_sum_256(acc, red);
-  if (threadIdx.x == 0) loss[0] = (accumulate ? loss[0] : 0.0f) + coef * total;
 }
 
 // runner.py:179-213 with the default criteria (L1 depth, MSE ray-drop on the label-smoothed mask, MSE intensity), all masked by

@@ -575,6 +575,63 @@ def lidar_losses(depth, image, gt, rays_d, alpha_d, alpha_r, alpha_i, smooth, sc
     return loss, g_depth, g_image, pts
 
 
+def ray_batch_patches(top, left, patch, pose, fov, H, W, image=None):
+    """l4ds_ray_batch (include/lidar4d_step.h): drawn patch corners (top / left [n_patch] int64 on the device) and the patch shape
+    ``patch`` = (px, py) -> rays_o, rays_d [1,n,3], gt [1,n,3] in ``image``'s dtype, fp32 or fp16 (None without ``image`` [H,W,3]),
+    inds [1,n], n = n_patch * px * py in patch-row-major order with the columns wrapping at W: the draw of
+    data/base_dataset.py:36-102 and the gather of kitti360_dataset.py:181-187 in one launch."""
+    from . import _step_lib
+    _chk(top, torch.int64, "top"), _chk(left, torch.int64, "left"), _chk(pose, torch.float32, "pose")
+    px, py = int(patch[0]), int(patch[1])
+    n_patch, dev = top.numel(), top.device
+    if left.numel() != n_patch:
+        raise ValueError(f"ray_batch_patches: {n_patch} top rows, {left.numel()} left columns")
+    n = n_patch * max(px, 0) * max(py, 0)
+    pose = pose.reshape(4, 4).contiguous()
+    rays_o = torch.empty(1, n, 3, dtype=torch.float32, device=dev)
+    rays_d = torch.empty(1, n, 3, dtype=torch.float32, device=dev)
+    inds = torch.empty(1, n, dtype=torch.int64, device=dev)
+    gt = None
+    if image is not None:
+        if image.dtype not in (torch.float32, torch.float16):
+            raise TypeError(f"image: expected torch.float32 or torch.float16, got {image.dtype}")
+        _chk(image, None, "image")
+        if image.numel() != int(H) * int(W) * 3:
+            raise ValueError(f"ray_batch_patches: image of {tuple(image.shape)} for H = {H}, W = {W}")
+        gt = torch.empty(1, n, 3, dtype=image.dtype, device=dev)
+    _step_lib.call("l4ds_ray_batch", _p(top), _p(left), n_patch, px, py, _p(pose), float(fov[0]), float(fov[1]), int(H), int(W),
+                   _p(image), int(image is not None and image.dtype == torch.float16), _p(rays_o), _p(rays_d), _p(gt), _p(inds), _stream())
+    return rays_o, rays_d, gt, inds
+
+
+def primary_losses_any(depth, image, gt, rays_d, kinds, alpha_d, alpha_r, alpha_i, smooth, delta, scale, want_points, want_gt32=False):
+    """l4ds_primary_losses (include/lidar4d_step.h): runner.py:179-213 for ``kinds`` = (depth, ray-drop, intensity) criteria out of
+    l1 / mse / bce / huber and ``gt`` [n,3] fp32 or fp16 -> loss [1], g_depth [n], g_image [n,2], pts [2,n,3] or None, and the fp32
+    copy of gt [n,3] or None."""
+    from . import _step_lib
+    for t, nm in ((depth, "depth"), (image, "image"), (rays_d, "rays_d")):
+        _chk(t, torch.float32, nm)
+    if gt.dtype not in (torch.float32, torch.float16):
+        raise TypeError(f"gt: expected torch.float32 or torch.float16, got {gt.dtype}")
+    _chk(gt, None, "gt")
+    for k in kinds:
+        if k not in _step_lib.KINDS:
+            raise ValueError(f"unknown loss criterion {k!r} (l1, mse, bce, huber)")
+    n, dev = depth.numel(), depth.device
+    if gt.numel() != 3 * n or image.numel() != 2 * n or (want_points and rays_d.numel() != 3 * n):
+        raise ValueError(f"primary_losses_any: {n} depths with image {tuple(image.shape)}, gt {tuple(gt.shape)}, rays_d {tuple(rays_d.shape)}")
+    loss = torch.empty(1, dtype=torch.float32, device=dev)
+    g_depth = torch.empty(n, dtype=torch.float32, device=dev)
+    g_image = torch.empty(n, 2, dtype=torch.float32, device=dev)
+    pts = torch.empty(2, n, 3, dtype=torch.float32, device=dev) if want_points else None
+    gt32 = torch.empty(n, 3, dtype=torch.float32, device=dev) if want_gt32 else None
+    ws = torch.empty(int(_step_lib.lib().l4ds_primary_losses_workspace(n)), dtype=torch.uint8, device=dev)
+    _step_lib.call("l4ds_primary_losses", _p(depth), _p(image), _p(gt), int(gt.dtype == torch.float16), _p(rays_d), n,
+                   *[_step_lib.KINDS[k] for k in kinds], float(alpha_d), float(alpha_r), float(alpha_i), float(smooth), float(delta),
+                   float(scale), _p(loss), _p(g_depth), _p(g_image), _p(pts), _p(gt32), _p(ws), _stream())
+    return loss, g_depth, g_image, pts, gt32
+
+
 def ray_chamfer_accumulate(pts, rays_d, gt, coef, scale, loss, g_depth):
     """Chamfer distance between pts[0] and pts[1] (l4d_chamfer_fwd), then loss += coef * sum(dist1 + dist2) and g_depth += its
     gradient wrt the rendered depth (l4d_ray_chamfer_grad): runner.py:215-220 with its autograd, three + five launches."""

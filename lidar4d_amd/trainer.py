@@ -6,7 +6,8 @@ optimizer main_lidar4d.py:298-305) plus the inference step of the evaluation / s
 (runner.py:438-470: staged render of a whole frame, U-Net ray-drop refinement, masking) and the optional ray-chamfer and
 scene-flow and line-of-sight loss terms (runner.py:215-276), the patch depth-gradient terms (runner.py:277-367), the
 optimiser-side semantics of the reference's AMP loop (GradScaler skip / backoff / growth, per-parameter Adam state:
-runner.py:102,506-508) and the per-epoch parameter EMA (runner.py:534-535).  Logging is out of scope.
+runner.py:102,506-508), the per-epoch parameter EMA (runner.py:534-535) and the run itself, ``Trainer.train`` (runner.py:686-719) on the
+splits of a preprocessed sequence (``lidar4d_amd.kitti360.KITTI360Dataset``).  Tensorboard, PNG output and progress bars are out of scope.
 """
 import os
 
@@ -20,16 +21,21 @@ from .params import bump_epoch
 
 def criterion(kind, scale=1.0):
     """The element-wise loss the reference selects with --depth_loss / --intensity_loss / --raydrop_loss
-    (main_lidar4d.py:63-66,183-196): l1, mse, bce (with logits) or huber (delta = 0.2 * scene scale), reduction none."""
+    (main_lidar4d.py:63-66,183-196): l1, mse, bce (with logits) or huber (delta = 0.2 * scene scale), reduction none.
+    Both arguments are cast to float first: the reference's step runs under autocast, whose fp32 policy does that for l1_loss,
+    mse_loss, huber_loss and binary_cross_entropy_with_logits -- which is what lets it take the fp16 ground truth it preloads.
+    fp32 inputs go through unchanged."""
     if kind == "l1":
-        return lambda a, b: (a - b).abs()
-    if kind == "mse":
-        return lambda a, b: (a - b) ** 2
-    if kind == "bce":
-        return lambda a, b: torch.nn.functional.binary_cross_entropy_with_logits(a, b, reduction="none")
-    if kind == "huber":
-        return lambda a, b: torch.nn.functional.huber_loss(a, b, reduction="none", delta=0.2 * scale)
-    raise ValueError(f"unknown loss criterion {kind!r} (l1, mse, bce, huber)")
+        fn = lambda a, b: (a - b).abs()
+    elif kind == "mse":
+        fn = lambda a, b: (a - b) ** 2
+    elif kind == "bce":
+        fn = lambda a, b: torch.nn.functional.binary_cross_entropy_with_logits(a, b, reduction="none")
+    elif kind == "huber":
+        fn = lambda a, b: torch.nn.functional.huber_loss(a, b, reduction="none", delta=0.2 * scale)
+    else:
+        raise ValueError(f"unknown loss criterion {kind!r} (l1, mse, bce, huber)")
+    return lambda a, b: fn(a.float(), b.float())
 
 
 def lidar_loss(outputs, images_lidar, alpha_d=1.0, alpha_r=0.01, alpha_i=0.1, smooth=0.2, depth_loss="l1",
@@ -52,19 +58,33 @@ def lidar_loss(outputs, images_lidar, alpha_d=1.0, alpha_r=0.01, alpha_i=0.1, sm
     return loss.sum()
 
 
+DEFAULT_CRITERIA = ("l1", "mse", "mse")  # depth, ray-drop, intensity (main_lidar4d.py:63-66)
+
+
 class _PrimaryLossFn(torch.autograd.Function):
-    """``lidar_loss`` (+ ``ray_chamfer_loss / world``) with the reference's default criteria as one autograd node on
-    csrc/glue.hip: forward = l4d_lidar_losses (+ l4d_chamfer_fwd, l4d_ray_chamfer_grad), which also leaves the gradients wrt
-    the rendered depth / image; backward = one launch that scales them by the upstream gradient (the loss scale, a device
-    scalar).  Replaces ~70 element-wise torch launches per step (runner.py:179-220 as torch evaluates it)."""
+    """``lidar_loss`` (+ ``ray_chamfer_loss / world``) as one autograd node: forward = l4d_lidar_losses (csrc/glue.hip) for the
+    reference's default criteria on fp32 ground truth, l4ds_primary_losses (csrc/stepglue.hip, liblidar4d_step.so) for fp16
+    ground truth or any other criterion (+ l4d_chamfer_fwd, l4d_ray_chamfer_grad), which also leaves the gradients wrt the
+    rendered depth / image; backward = one launch that scales them by the upstream gradient (the loss scale, a device scalar).
+    Replaces ~70 element-wise torch launches per step (runner.py:179-220 as torch evaluates it)."""
 
     @staticmethod
-    def forward(ctx, depth, image, gt, rays_d, alpha_d, alpha_r, alpha_i, smooth, scale, chamfer, world):
+    def forward(ctx, depth, image, gt, rays_d, alpha_d, alpha_r, alpha_i, smooth, scale, chamfer, world, kinds):
         c = lambda t, *shape: t.detach().to(torch.float32).reshape(*shape).contiguous()
         n = depth.numel()
-        gt_c, rd_c = c(gt, n, 3), c(rays_d, n, 3)
-        loss, g_depth, g_image, pts = ops.lidar_losses(c(depth, n), c(image, n, 2), gt_c, rd_c, alpha_d, alpha_r, alpha_i, smooth, scale,
-                                                       want_points=bool(chamfer))
+        rd_c = c(rays_d, n, 3)
+        if gt.dtype == torch.float16 or tuple(kinds) != DEFAULT_CRITERIA:
+            gt_c = gt.detach().reshape(n, 3)
+            gt_c = (gt_c if gt_c.dtype == torch.float16 else gt_c.to(torch.float32)).contiguous()
+            want32 = bool(chamfer) and gt_c.dtype == torch.float16  # (ops.ray_chamfer_accumulate reads the mask as fp32)
+            loss, g_depth, g_image, pts, gt32 = ops.primary_losses_any(c(depth, n), c(image, n, 2), gt_c, rd_c, kinds, alpha_d, alpha_r,
+                                                                       alpha_i, smooth, 0.2 * scale, scale, want_points=bool(chamfer),
+                                                                       want_gt32=want32)
+            gt_c = gt32 if want32 else gt_c
+        else:
+            gt_c = c(gt, n, 3)
+            loss, g_depth, g_image, pts = ops.lidar_losses(c(depth, n), c(image, n, 2), gt_c, rd_c, alpha_d, alpha_r, alpha_i, smooth,
+                                                           scale, want_points=bool(chamfer))
         if chamfer:
             ops.ray_chamfer_accumulate(pts, rd_c, gt_c, 0.5 / max(n, 1) / world, scale, loss, g_depth)
         ctx.save_for_backward(g_depth, g_image)
@@ -75,14 +95,19 @@ class _PrimaryLossFn(torch.autograd.Function):
     def backward(ctx, g):
         g_depth, g_image = ctx.saved_tensors
         d, i = ops.scale_buffers(g_depth, g_image, g.detach().to(torch.float32).reshape(1).contiguous())
-        return (d.view(ctx.shapes[0]), i.view(ctx.shapes[1])) + (None,) * 9
+        return (d.view(ctx.shapes[0]), i.view(ctx.shapes[1])) + (None,) * 10
 
 
-def primary_losses(outputs, data, scale, chamfer=True, world=1, alpha_d=1.0, alpha_r=0.01, alpha_i=0.1, smooth=0.2):
-    """= lidar_loss(outputs, images) [+ ray_chamfer_loss(outputs, data, scale) / world] for the default criteria (L1 / MSE /
-    MSE), evaluated by the fused HIP path (``_PrimaryLossFn``)."""
+def primary_losses(outputs, data, scale, chamfer=True, world=1, alpha_d=1.0, alpha_r=0.01, alpha_i=0.1, smooth=0.2, depth_loss="l1",
+                   raydrop_loss="mse", intensity_loss="mse"):
+    """= lidar_loss(outputs, images, ...) [+ ray_chamfer_loss(outputs, data, scale) / world], evaluated by the fused HIP path
+    (``_PrimaryLossFn``) for any of the four criteria per term and fp32 or fp16 ``images_lidar``."""
+    kinds = (depth_loss, raydrop_loss, intensity_loss)
+    for k in kinds:
+        if k not in ("l1", "mse", "bce", "huber"):
+            raise ValueError(f"unknown loss criterion {k!r} (l1, mse, bce, huber)")
     return _PrimaryLossFn.apply(outputs["depth_lidar"], outputs["image_lidar"], data["images_lidar"], data["rays_d_lidar"],
-                                alpha_d, alpha_r, alpha_i, smooth, scale, chamfer, world)
+                                alpha_d, alpha_r, alpha_i, smooth, scale, chamfer, world, kinds)
 
 
 def frame_index(time_lidar, num_frames):
@@ -313,9 +338,24 @@ def patch_depth_grad_loss(pred_depth, gt_depth, gt_raydrop, patch_size, scale, a
                                   alpha_grad_norm, alpha_spatial, alpha_tv)
 
 
+def dataset_frames(dataset):
+    """The frames a dataset holds, as its ``batch_for`` / ``frame`` number them: ``dataset.frames()`` where there is one (a split
+    of a real sequence holds fewer frames than the sequence is long), ``range(dataset.num_frames)`` otherwise."""
+    return dataset.frames() if hasattr(dataset, "frames") else range(dataset.num_frames)
+
+
+def sequence_index(dataset, k):
+    """Held frame ``k``'s place in the sequence, = ``frame_index(its time, dataset.num_frames)``: the key of its point clouds."""
+    return dataset.sequence_index(k) if hasattr(dataset, "sequence_index") else k
+
+
 def process_pointcloud(dataset, ground_split=None, removal=None):
     """runner.py:923-951 on the device: per frame, ground-truth range image -> points (lidar4d_amd.convert) -> split into
-    non-ground / ground -> scene units and world frame.  Returns (pc_list, pc_ground_list), dicts keyed by str(frame).
+    non-ground / ground -> scene units and world frame.  Returns (pc_list, pc_ground_list), dicts keyed by str(frame's
+    index in the sequence) (runner.py:949).  The dataset gives ``images`` / ``poses`` (SyntheticKitti360) or ``images_lidar`` /
+    ``poses_lidar`` (KITTI360Dataset).  fp16 ground truth: the reference's numpy expression ``depth * mask / scale`` stays in
+    half -- the python float ``scale`` is taken to half too -- before the conversion widens it
+    (tests/golden/train_step_losses_f16.npz holds what it gives).
     The reference separates the ground with RANSAC + open3d outlier removal (utils/misc.py:128-154):
     ``removal(points[N,3]) -> (non_ground, ground)`` does that when given -- ``lidar4d_amd.pointprep.point_removal`` is the
     device-side counterpart, the choice for a real sequence -- and takes precedence over ``ground_split``.  Without it,
@@ -325,20 +365,27 @@ def process_pointcloud(dataset, ground_split=None, removal=None):
     if ground_split is None:
         ground_split = lambda pts: (pts[:, 2] + 1.7).abs() < 0.15
     pc_list, pc_ground_list = {}, {}
-    for k in range(dataset.num_frames):
-        img = dataset.images[k]
+    images = dataset.images if hasattr(dataset, "images") else dataset.images_lidar
+    poses = dataset.poses if hasattr(dataset, "poses") else dataset.poses_lidar
+    for k in dataset_frames(dataset):
+        img = images[k]
         gt_depth = img[..., 2] * img[..., 0]
-        pts = pano_to_lidar(gt_depth / dataset.scale, dataset.fov)          # metres, sensor frame
-        pose = dataset.poses[k]
+        if gt_depth.dtype == torch.float16:
+            metres = (gt_depth / torch.tensor(dataset.scale, dtype=torch.float16, device=gt_depth.device)).float()
+        else:
+            metres = gt_depth / dataset.scale
+        pts = pano_to_lidar(metres, dataset.fov)                            # metres, sensor frame
+        pose = poses[k].to(pts.device)
         to_world = lambda q: (q * dataset.scale) @ pose[:3, :3].T + pose[:3, 3]
+        key = f"{sequence_index(dataset, k)}"
         if removal is not None:
             non_ground, ground = removal(pts)
-            pc_list[f"{k}"] = to_world(non_ground).contiguous()
-            pc_ground_list[f"{k}"] = to_world(ground).contiguous()
+            pc_list[key] = to_world(non_ground).contiguous()
+            pc_ground_list[key] = to_world(ground).contiguous()
             continue
         is_ground = ground_split(pts)
-        pc_list[f"{k}"] = to_world(pts[~is_ground]).contiguous()
-        pc_ground_list[f"{k}"] = to_world(pts[is_ground]).contiguous()
+        pc_list[key] = to_world(pts[~is_ground]).contiguous()
+        pc_ground_list[key] = to_world(pts[is_ground]).contiguous()
     return pc_list, pc_ground_list
 
 
@@ -856,7 +903,7 @@ class Trainer:
                  grad_transport="fp32", graph_batch_inside=True, flow_loss_stream=True, point_removal=None,
                  depth_grad_loss="l1", sobel_grad=False, grad_loss=True, grad_norm_smooth=False, spatial_smooth=False,
                  tv_loss=False, alpha_grad=0.1, alpha_grad_norm=0.1, alpha_spatial=0.1, alpha_tv=0.1, fused_patch=None,
-                 change_patch_size_lidar=None, change_patch_size_epoch=2):
+                 change_patch_size_lidar=None, change_patch_size_epoch=2, pointcloud_dataset=None):
         """Defaults follow the reference's default run: the ray chamfer term is always part of its step
         (runner.py:215-220) and ``--flow_loss`` defaults to True (main_lidar4d.py:67).
         chamfer: a mean over the rank's own rays, so under data parallelism it is scaled by 1/world before the SUM
@@ -872,13 +919,17 @@ class Trainer:
         change_patch_size_lidar / change_patch_size_epoch: the reference's patch epochs (runner.py:694-705).  None (default)
         leaves ``dataset.patch_size_lidar`` alone; a patch size such as [2, 8] -- the reference's default -- is set on the
         dataset before the batch of every step of an epoch with ``epoch % change_patch_size_epoch == 0`` (epochs count from 1),
-        and 1 in the other epochs."""
+        and 1 in the other epochs.
+        pointcloud_dataset: the split the scene-flow clouds are built from -- the reference hands ``train()`` its ``refine``
+        loader for that (runner.py:691-692: the training frames, served whole); default: ``dataset``."""
         self.model, self.dataset, self.num_steps, self.chamfer = model, dataset, num_steps, chamfer
         self.flow, self.urf, self.iters = flow, urf, iters
         self.loss_kinds = dict(depth_loss=depth_loss, raydrop_loss=raydrop_loss, intensity_loss=intensity_loss)
-        # the default criteria run as one fused node (primary_losses); any other choice, or fused_losses=False, takes the torch
+        for kind in self.loss_kinds.values():
+            criterion(kind)  # (refuses an unknown one)
+        # the primary losses run as one fused node (primary_losses) whatever the criteria; fused_losses=False takes the torch
         # restatement of runner.py:179-220 (lidar_loss / ray_chamfer_loss; what the tests compare the fused nodes with)
-        self.fused_losses = (depth_loss, raydrop_loss, intensity_loss) == ("l1", "mse", "mse") and bool(fused_losses)
+        self.fused_losses = bool(fused_losses)
         self.fused_flow_loss = bool(fused_losses)  # the scene-flow term as one autograd node (_SceneFlowLossFn)
         self.fused_urf = bool(fused_losses)        # the line-of-sight term as one autograd node (_LineOfSightLossFn), any criteria
         self.fused_patch = bool(fused_losses) if fused_patch is None else bool(fused_patch)  # the patch terms as one node (_PatchGradLossFn)
@@ -901,10 +952,12 @@ class Trainer:
         self.flow_loss_stream = bool(flow_loss_stream)
         self._flow_stream = None
         self.ema = FlatEMA(model, ema_decay) if ema_decay is not None else None  # runner.py:97-98
-        self.epoch_steps = epoch_steps if epoch_steps is not None else getattr(dataset, "num_frames", 1)
+        self.epoch_steps = epoch_steps if epoch_steps is not None else \
+            (len(dataset.frames()) if hasattr(dataset, "frames") else getattr(dataset, "num_frames", 1))
         self.local_step = 0
         if flow:
-            self.pc_list, self.pc_ground_list = process_pointcloud(dataset, removal=point_removal)
+            self.pc_list, self.pc_ground_list = process_pointcloud(dataset if pointcloud_dataset is None else pointcloud_dataset,
+                                                                   removal=point_removal)
         self.opt = FlatAdam(model, lr=lr, iters=iters)
         self.scaler = DynamicLossScaler(model._store.flat.device, init_scale=init_scale) if loss_scaler else None
         model.reference_grad_none = False  # untouched time slices are gated on the device (FlatAdam), no host read-back
@@ -921,7 +974,8 @@ class Trainer:
         """The reference's training loss (runner.py:179-276,277-367) for one batch and its render outputs.
         flow_term: the scene-flow term if the caller has evaluated it already (train_step on a side stream)."""
         if self.fused_losses and out["depth_lidar"].is_cuda:
-            loss = primary_losses(out, data, self.dataset.scale, chamfer=self.chamfer, world=self.world)
+            loss = primary_losses(out, data, self.dataset.scale, chamfer=self.chamfer, world=self.world,
+                                  **getattr(self, "loss_kinds", {}))
         else:
             loss = lidar_loss(out, data["images_lidar"], scale=self.dataset.scale, **self.loss_kinds)
             if self.chamfer:
@@ -982,9 +1036,10 @@ class Trainer:
         process group), a dataset that draws its batch on the device (``batch_for`` + ``register`` of its generator), the
         patch terms and the line-of-sight term only as their fused nodes (``fused_patch``; ``fused_urf``: its tolerance follows
         the optimiser's schedule on the device, the torch restatement ``urf_loss`` computes it on the host from
-        ``opt.step_count``)."""
+        ``opt.step_count``).  A ``KITTI360Dataset`` draws on the device when it is preloaded there (``device_batches``)."""
         patches = getattr(self.dataset, "patch_size_lidar", 1) != 1 or getattr(self, "change_patch_size_lidar", None) is not None
         return (self.reducer is None and (not self.urf or getattr(self, "fused_urf", False)) and hasattr(self.dataset, "batch_for") and hasattr(self.dataset, "next_frame")
+                and getattr(self.dataset, "device_batches", True)
                 and (not patches or getattr(self, "fused_patch", False)) and self.model._store.flat.is_cuda)
 
     def train_step_graphed(self, frame=None):
@@ -1089,21 +1144,81 @@ class Trainer:
             self.scaler.update()                 # runner.py:508
         return loss
 
+    def save(self, path, epoch=0, stats=None):
+        """A full checkpoint in the reference's format (lidar4d_amd.checkpoint) with this trainer's step count."""
+        from .checkpoint import save_checkpoint
+        return save_checkpoint(path, self.model, self.opt, self.ema, self.scaler, epoch=epoch, global_step=self.local_step, stats=stats)
+
+    def load(self, path):
+        """Load a full checkpoint; the step count (and with it the epoch and patch-epoch schedule) continues from it."""
+        from .checkpoint import load_checkpoint
+        info = load_checkpoint(path, self.model, self.opt, self.ema, self.scaler)
+        self.local_step = int(info["global_step"])
+        return info
+
+    def train(self, valid_dataset=None, refine_dataset=None, max_epochs=None, eval_interval=100, workspace=None, graphed=None,
+              name="lidar4d", refine_iters=1000, refine_batch_size=None, refine_rng=None, max_ray_batch=4096, log=None):
+        """runner.py:686-719, the reference's training run, without tensorboard, PNG output and progress bar: ``max_epochs``
+        epochs (default ``ceil(iters / frames held)``, main_lidar4d.py:324) of one step per held frame in the dataset's
+        permutation, continuing after the epochs already made (``local_step``); patch epochs as ``change_patch_size_lidar`` says;
+        the EMA updated once per epoch; with a ``workspace`` a full checkpoint ``<workspace>/checkpoints/<name>_ep<epoch>.pth``
+        after every epoch; ``evaluate(valid_dataset, refine=False)`` every ``eval_interval`` epochs (main_lidar4d.py:93); at the
+        end the U-Net refinement on ``refine_dataset`` (``collect_refine_data`` + ``refine_unet`` over ``refine_iters`` steps).
+        Either dataset may be None: that stage is left out.  graphed (default ``graphs_supported()``): steps are replays of
+        captured graphs.  log: a callable for the log lines.
+        Returns dict(loss = [mean training loss per epoch], results = [(epoch, evaluate()'s dict)], refine_loss = [U-Net losses])."""
+        import math
+        log = log if log is not None else (lambda line: None)
+        graphed = self.graphs_supported() if graphed is None else bool(graphed)
+        frames = len(dataset_frames(self.dataset))
+        if self.epoch_steps != frames:
+            raise ValueError(f"Trainer.train: epoch_steps = {self.epoch_steps}, but an epoch of the dataset has {frames} frames")
+        if max_epochs is None:
+            max_epochs = int(math.ceil(self.iters / frames))
+        history = {"loss": [], "results": [], "refine_loss": []}
+        self.model.train()
+        for epoch in range(self.local_step // frames + 1, max_epochs + 1):
+            log(f"==> Start Training Epoch {epoch}, lr={self.opt.lr():.6f} ...")
+            losses = []
+            for _ in range(frames):
+                losses.append((self.train_step_graphed() if graphed else self.train_step()).detach())
+            average = float(torch.stack([l.float().reshape(()) for l in losses]).mean())  # one read-back per epoch
+            history["loss"].append(average)
+            log(f"average_loss: {average}.")
+            if workspace is not None:
+                self.save(os.path.join(workspace, "checkpoints", f"{name}_ep{epoch:04d}.pth"), epoch=epoch,
+                          stats={"loss": list(history["loss"]), "valid_loss": [r["loss"] for _, r in history["results"]],
+                                 "results": [], "checkpoints": [], "best_result": None})
+            if valid_dataset is not None and epoch % eval_interval == 0:
+                result = self.evaluate(valid_dataset, refine=False, max_ray_batch=max_ray_batch,
+                                       raydrop_loss=self.loss_kinds["raydrop_loss"])
+                history["results"].append((epoch, result))
+                for line in result["report"]:
+                    log(line)
+        if refine_dataset is not None:
+            log("Preparing the ray-drop refinement ...")
+            raydrop_input, raydrop_gt = self.collect_refine_data(refine_dataset, max_ray_batch=max_ray_batch)
+            history["refine_loss"] = refine_unet(self.model.unet, raydrop_input, raydrop_gt, epochs=refine_iters,
+                                                 batch_size=refine_batch_size, rng=refine_rng, log=log)
+        return history
+
     def end_epoch(self):
         """runner.py:534-535: the parameter EMA is updated once per epoch, after the loop over the loader."""
         if self.ema is not None:
             self.ema.update()
 
     @torch.no_grad()
-    def collect_refine_data(self, frames=None, max_ray_batch=4096):
-        """runner.py:824-863: render every training frame with the (frozen) field and stack what the U-Net sees --
+    def collect_refine_data(self, dataset=None, frames=None, max_ray_batch=4096):
+        """runner.py:824-863: render every frame of ``dataset`` (the reference's ``refine`` split: the training frames served
+        whole; default: the trainer's own dataset) with the (frozen) field and stack what the U-Net sees --
         returns (raydrop_input [B, 3, H, W], raydrop_gt [B, 1, H, W]) for ``refine_unet``."""
+        dataset = self.dataset if dataset is None else dataset
         self.model.eval()
         if self.ema is not None:
             self.ema.copy_to()  # the reference refines on the EMA weights and drops the raw ones (runner.py:819-821)
         inputs, gts = [], []
-        for k in (range(self.dataset.num_frames) if frames is None else frames):
-            fr = self.dataset.frame(k)
+        for k in (dataset_frames(dataset) if frames is None else frames):
+            fr = dataset.frame(k)
             H, W = fr["H_lidar"], fr["W_lidar"]
             out = self.model.render(fr["rays_o_lidar"], fr["rays_d_lidar"], fr["time"], staged=True, perturb=False,
                                     max_ray_batch=max_ray_batch, num_steps=self.num_steps)
@@ -1136,10 +1251,10 @@ class Trainer:
         return pred_raydrop, pred_intensity, pred_depth
 
     @torch.no_grad()
-    def evaluate(self, frames=None, refine=True, max_ray_batch=4096, raydrop_loss="mse", intensity_scale=1.0, raydrop_ratio=0.5,
+    def evaluate(self, dataset=None, frames=None, refine=True, max_ray_batch=4096, raydrop_loss="mse", intensity_scale=1.0, raydrop_ratio=0.5,
                  lpips_fn=None):
-        """runner.py:379-434,553-682 without the PNG, progress-bar and tensorboard output: every frame (default: all of the
-        dataset's) is rendered on the EMA weights if there are any, scored by the evaluation loss of runner.py:418-422 (the
+        """runner.py:379-434,553-682 without the PNG, progress-bar and tensorboard output: every frame (default: all) of
+        ``dataset`` (default: the trainer's own; the reference evaluates its ``val`` split) is rendered on the EMA weights if there are any, scored by the evaluation loss of runner.py:418-422 (the
         trainer's criteria, the reference's default weights 1 / 0.01 / 0.1) and fed to the four meters of
         main_lidar4d.py:199-204 in their order.  Intensity, depth and points meters see the predictions masked by
         ``pred_raydrop > 0.5``.  The raw weights are back in place afterwards.
@@ -1147,11 +1262,12 @@ class Trainer:
         four report() lines).  The image meters and the loss read nothing back from the device before the final measure() calls;
         PointsMeter reads the sizes of its two clouds per frame, as it always has."""
         from .metrics import DepthMeter, IntensityMeter, PointsMeter, RaydropMeter
-        scale = self.dataset.scale
+        dataset = self.dataset if dataset is None else dataset
+        scale = dataset.scale
         meters = {"raydrop": RaydropMeter(ratio=raydrop_ratio),
                   "intensity": IntensityMeter(scale=intensity_scale, lpips_fn=lpips_fn),
                   "depth": DepthMeter(scale=scale, lpips_fn=lpips_fn),
-                  "points": PointsMeter(scale=scale, intrinsics=self.dataset.fov)}
+                  "points": PointsMeter(scale=scale, intrinsics=dataset.fov)}
         crit = {k: criterion(self.loss_kinds[f"{k}_loss"], scale) for k in ("depth", "raydrop", "intensity")}
         alpha_d, alpha_r, alpha_i = 1.0, 0.01, 0.1  # main_lidar4d.py's defaults, as in lidar_loss
         was_training = self.model.training
@@ -1161,11 +1277,11 @@ class Trainer:
             self.ema.copy_to()
         try:
             total, count = None, 0
-            for k in (range(self.dataset.num_frames) if frames is None else frames):
-                fr = self.dataset.frame(k)
+            for k in (dataset_frames(dataset) if frames is None else frames):
+                fr = dataset.frame(k)
                 pred_raydrop, pred_intensity, pred_depth = self.test_step(fr, refine=refine, max_ray_batch=max_ray_batch,
                                                                           raydrop_loss=raydrop_loss, alpha_r=0)  # unmasked
-                images = fr["images_lidar"]
+                images = fr["images_lidar"].float()  # (fp16 ground truth widens exactly; the mask is 0 / 1)
                 gt_raydrop = images[:, :, :, 0]
                 gt_intensity = images[:, :, :, 1] * gt_raydrop
                 gt_depth = images[:, :, :, 2] * gt_raydrop
