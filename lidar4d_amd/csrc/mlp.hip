@@ -16,14 +16,19 @@
 // so that tiles 2ks and 2ks+1 together give the lane neurons 32ks+8g .. 32ks+8g+7 of its row: exactly
 // the next layer's B fragment.  No LDS, no shuffles between layers.
 //
-// Backward needs contractions over the BATCH (dW = dZ^T H).  Those want "8 consecutive rows per lane".
-// Instead of transposing through LDS the same quantities are produced a second time with the batch as
-// the M dimension ("orientation 2": C'[row][feature], lane = feature, 4 rows per tile), using the
-// chain-layout registers as A operand, and raw inputs are transposed with an identity-matrix MFMA
-// (exact).  Macro tile = 32 rows = chain tiles a=0,1 with row(a, i) = 8*(i>>2) + 4a + (i&3), which
-// makes the two orientation-2 tiles give the lane rows 8g .. 8g+7.
-// MFMA utilisation is irrelevant here (~2 % of peak at target rate); the doubled MFMA work
-// buys a kernel with no LDS traffic in the loop and no barriers.
+// Backward needs contractions over the BATCH (dW = dZ^T H).  Those want "8 consecutive rows per lane":
+// lane (i, g) holds rows 8g .. 8g+7 of feature 16 nt + i, as B operand (H, X) or as A operand (dZ).
+// Macro tile = 32 rows = chain tiles a=0,1 with row(a, i) = 8*(i>>2) + 4a + (i&3).  Every such operand is
+// the transpose of something the chain already holds -- dy, the hidden activations and x as loaded (or
+// recomputed), each layer's gated dZ as the chain produced it for the next layer -- and goes through a
+// wave-private LDS image (mlp_dev.h BwdStage): ds_write_b128 from the chain layout, two ds_read_b64_tr_b16
+// (gfx950's transposing read) per operand.  A wavefront's DS operations execute in order, so there is no
+// barrier, and one region is reused for dy, every layer's activations and x in turn; dZ has a second one.
+// The reads of a section are issued ahead of that section's chain MFMAs, which need none of them.
+// (Until this form the batch-major operands were produced a second time on the matrix cores: raw inputs by an
+// identity-matrix MFMA + conversions, dZ by a second dZ W product with the batch as M dimension and a second
+// ReLU gate: 54 of the attribute tile's 170 MFMAs.)  The transposed reads run with EXEC all ones: they sit
+// in wave-uniform control flow only, and rows past the end of the last tile are staged as the zeros they are.
 #include "common.h"
 #include "wave_dev.h"
 
@@ -231,13 +236,12 @@ __global__ void __launch_bounds__(256) mlp_fwd_kernel(const half_t* __restrict__
 template <int IN_TILES, int NH>
 struct BwdFrags {
   static constexpr int KS_IN = (IN_TILES + 1) / 2;
-  // W_o^T : chain (permuted rows) 4, orientation-2 (natural rows) 4
+  // W_o^T : chain (permuted rows) 4
   static constexpr int WOT_P = 0;
-  static constexpr int WOT_N = 4;
-  // hidden W_l^T, l = NH .. 2: per layer chain 8 + natural 8
-  static constexpr int WH = 8;
+  // hidden W_l^T, l = NH .. 2: per layer chain 8
+  static constexpr int WH = 4;
   // W_1^T natural: IN_TILES x 2
-  static constexpr int W1T = WH + (NH - 1) * 16;
+  static constexpr int W1T = WH + (NH - 1) * 8;
   static constexpr int NF = W1T + IN_TILES * 2;
 };
 
@@ -290,25 +294,31 @@ __global__ void __launch_bounds__(256, (IN_TILES == 1 && NH <= 2 ? MLP_BWD_NARRO
   constexpr int KS_IN = L::KS_IN;
   constexpr int NF_FWD = RECOMP ? 4 * KS_IN + (NH - 1) * 8 : 0;  // forward chain fragments (layers 1 .. NH), as in mlp_fwd_kernel
   __shared__ uint4 frags[L::NF + NF_FWD][64];
+  // staging image of this wavefront (mlp_dev.h): one region, reused for dy, every hidden layer's activations and x in turn -- a
+  // wavefront's DS operations execute in order, so an image may be overwritten once the reads of the previous one are ISSUED, and
+  // no barrier is involved.  x: only the 32-column groups that hold the column tiles COL_LO .. COL_HI - 1.
+  constexpr int XKS_LO = COL_LO / 2, XKS_HI = (COL_HI + 1) / 2;
+  using SG = BwdStage<(XKS_HI - XKS_LO > 2 ? XKS_HI - XKS_LO : 2)>;
+  __shared__ uint4 stage[4][2 * SG::BYTES / 16];
 
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const int i = lane & 15, g = lane >> 4;
+  lds_u8* const stage_base = reinterpret_cast<lds_u8*>((__attribute__((address_space(3))) void*)&stage[wave][0]);
+  lds_u8* const stage_wr = stage_base + (i >> 2) * SG::BLK + (i & 3) * SG::PITCH + 16 * g;
+  lds_u8* const stage_rd = stage_base + g * SG::BLK + (i >> 2) * SG::PITCH + 8 * (i & 3);
   const half_t* W1 = weights;
   const half_t* Wo = weights + HID * IN_PAD + (NH - 1) * HID * HID;
 
   for (int f = wave; f < L::NF; f += 4) {
     h8 v;
     if (f < L::WH) {
-      const int mt = f & 3;
-      const int row = (f < 4) ? perm_row(mt, i) : 16 * mt + i;
-      v = build_frag(Wo, 16, HID, 1, row, 8 * g);  // k = output index m (only 16 real)
+      v = build_frag(Wo, 16, HID, 1, perm_row(f, i), 8 * g);  // k = output index m (only 16 real)
     } else if (f < L::W1T) {
-      const int q = f - L::WH, li = q / 16, r = q % 16;  // li = 0 -> layer NH, 1 -> NH-1 ...
+      const int q = f - L::WH, li = q / 8, r = q % 8;  // li = 0 -> layer NH, 1 -> NH-1 ...
       const int layer = NH - li;                         // hidden layer index (>= 2)
       const half_t* Wl = weights + HID * IN_PAD + (layer - 2) * HID * HID;
-      const int nat = r / 8, mt = (r % 8) / 2, ks = r % 2;
-      const int row = nat ? 16 * mt + i : perm_row(mt, i);
-      v = build_frag(Wl, HID, HID, 1, row, 32 * ks + 8 * g);
+      const int mt = r / 2, ks = r % 2;
+      v = build_frag(Wl, HID, HID, 1, perm_row(mt, i), 32 * ks + 8 * g);
     } else {
       const int q = f - L::W1T, mt = q / 2, ks = q % 2;
       v = build_frag(W1, HID, IN_PAD, 1, 16 * mt + i, 32 * ks + 8 * g, src.cperm);
@@ -330,7 +340,6 @@ __global__ void __launch_bounds__(256, (IN_TILES == 1 && NH <= 2 ? MLP_BWD_NARRO
   }
   __syncthreads();
   auto FR = [&](int f) -> h8 { uint4 u = frags[f][lane]; return *reinterpret_cast<h8*>(&u); };
-  const h8 I0 = ident_frag(lane, 0), I1 = ident_frag(lane, 1);
 
   // dW accumulators, C layout: [m = 16*mt + 4g + r][k = 16*nt + i]
   f4 dWo[4];
@@ -499,78 +508,158 @@ __global__ void __launch_bounds__(256, (IN_TILES == 1 && NH <= 2 ? MLP_BWD_NARRO
     h8 hrec[RECOMP ? NH : 1][2][2];
     if (RECOMP) {
 #pragma unroll
-      for (int a = 0; a < 2; ++a) {
+      for (int a = 0; a < 2; ++a)
 #pragma unroll
-        for (int ks = 0; ks < KS_IN; ++ks) {
-          xf[a][ks] = *reinterpret_cast<h8*>(&cur.x[a][ks]);
-        }
-        f4 acc[4];
+        for (int ks = 0; ks < KS_IN; ++ks) xf[a][ks] = *reinterpret_cast<h8*>(&cur.x[a][ks]);
+      // Both chain tiles share a weight fragment, and the fragments of neuron tile mt + 1 are requested before the MFMAs of tile mt:
+      // the empty asm on the current fragments (behind the barrier that holds the requests) keeps the scheduler from pulling the
+      // MFMAs in front of the requests, which left every pair of fragments waited for right behind its own request.
+      typedef uint32_t FrU4 __attribute__((ext_vector_type(4)));
+      f4 acc[2][4];
+      {
+        h8 wn[KS_IN];
+#pragma unroll
+        for (int ks = 0; ks < KS_IN; ++ks) wn[ks] = FR(L::NF + ks);
 #pragma unroll
         for (int mt = 0; mt < 4; ++mt) {
-          acc[mt] = f4{0, 0, 0, 0};
+          h8 wc[KS_IN];
 #pragma unroll
-          for (int ks = 0; ks < KS_IN; ++ks) acc[mt] = MFMA(FR(L::NF + mt * KS_IN + ks), xf[a][ks], acc[mt]);
-        }
-        hrec[0][a][0] = relu_pack(acc[0], acc[1]);
-        hrec[0][a][1] = relu_pack(acc[2], acc[3]);
+          for (int ks = 0; ks < KS_IN; ++ks) wc[ks] = wn[ks];
+          if (mt + 1 < 4) {
 #pragma unroll
-        for (int l = 1; l < NH; ++l) {
-          const int base = L::NF + 4 * KS_IN + (l - 1) * 8;
-#pragma unroll
-          for (int mt = 0; mt < 4; ++mt) {
-            acc[mt] = f4{0, 0, 0, 0};
-            acc[mt] = MFMA(FR(base + mt * 2 + 0), hrec[l - 1][a][0], acc[mt]);
-            acc[mt] = MFMA(FR(base + mt * 2 + 1), hrec[l - 1][a][1], acc[mt]);
+            for (int ks = 0; ks < KS_IN; ++ks) wn[ks] = FR(L::NF + (mt + 1) * KS_IN + ks);
           }
-          hrec[l][a][0] = relu_pack(acc[0], acc[1]);
-          hrec[l][a][1] = relu_pack(acc[2], acc[3]);
+          asm volatile("" ::: "memory");
+#pragma unroll
+          for (int ks = 0; ks < KS_IN; ++ks) asm volatile("" : "+v"(reinterpret_cast<FrU4&>(wc[ks])));
+#pragma unroll
+          for (int a = 0; a < 2; ++a) {
+            acc[a][mt] = f4{0, 0, 0, 0};
+#pragma unroll
+            for (int ks = 0; ks < KS_IN; ++ks) acc[a][mt] = MFMA(wc[ks], xf[a][ks], acc[a][mt]);
+          }
+        }
+      }
+#pragma unroll
+      for (int a = 0; a < 2; ++a) {
+        hrec[0][a][0] = relu_pack(acc[a][0], acc[a][1]);
+        hrec[0][a][1] = relu_pack(acc[a][2], acc[a][3]);
+      }
+#pragma unroll
+      for (int l = 1; l < NH; ++l) {
+        const int base = L::NF + 4 * KS_IN + (l - 1) * 8;
+        h8 wn[2];
+#pragma unroll
+        for (int ks = 0; ks < 2; ++ks) wn[ks] = FR(base + ks);
+#pragma unroll
+        for (int mt = 0; mt < 4; ++mt) {
+          h8 wc[2];
+#pragma unroll
+          for (int ks = 0; ks < 2; ++ks) wc[ks] = wn[ks];
+          if (mt + 1 < 4) {
+#pragma unroll
+            for (int ks = 0; ks < 2; ++ks) wn[ks] = FR(base + (mt + 1) * 2 + ks);
+          }
+          asm volatile("" ::: "memory");
+#pragma unroll
+          for (int ks = 0; ks < 2; ++ks) asm volatile("" : "+v"(reinterpret_cast<FrU4&>(wc[ks])));
+#pragma unroll
+          for (int a = 0; a < 2; ++a) {
+            acc[a][mt] = f4{0, 0, 0, 0};
+            acc[a][mt] = MFMA(wc[0], hrec[l - 1][a][0], acc[a][mt]);
+            acc[a][mt] = MFMA(wc[1], hrec[l - 1][a][1], acc[a][mt]);
+          }
+        }
+#pragma unroll
+        for (int a = 0; a < 2; ++a) {
+          hrec[l][a][0] = relu_pack(acc[a][0], acc[a][1]);
+          hrec[l][a][1] = relu_pack(acc[a][2], acc[a][3]);
         }
       }
     }
     // ---- output layer ----------------------------------------------------------------------
     h8 dzf[2][2];  // chain B fragments of the current layer's dZ: [a][ks]
-    h8 dzT[4];     // orientation-2: lane = feature 16*nt + i, 8 rows
+    h8 dzT[4];     // the same dZ batch-major (A operand of the dW MFMAs): lane = feature 16*nt + i, rows 8g .. 8g+7
     h8 dyT;
 #pragma unroll
     for (int a = 0; a < 2; ++a) {
       dzf[a][0] = *reinterpret_cast<h8*>(&cur.dy[a]);
     }
-    {
-      f4 t0 = MFMA(dzf[0][0], I0, (f4{0, 0, 0, 0}));
-      f4 t1 = MFMA(dzf[1][0], I0, (f4{0, 0, 0, 0}));
+    // Batch-major operands (dyT, hT, xT, dzT: rows 8g .. 8g+7 of feature 16 nt + i) come out of the staging image.  A group = an
+    // image's ds_write_b128 and its transposed reads.  A section (one layer) runs: [groups of its activations] -> chain MFMAs and
+    // ReLU gate (they need none of the reads) -> dW MFMAs (hT from this section's group, dzT from the previous section's) -> group of
+    // the dZ just made.  The empty asm after a group keeps the next image's writes behind this one's reads and the group where it is.
+    // All of it is in wave-uniform control flow, rows past the end of the last tile included (finish_tile zeroed them; recomputed
+    // activations of a zero row are zero): pad, don't mask.
+    auto hid = [&](int layer, int a, int ks) -> uint4 {  // activations of hidden layer `layer` (1-based), chain layout
+      return RECOMP ? *reinterpret_cast<const uint4*>(&hrec[RECOMP ? layer - 1 : 0][a][ks]) : cur.h[NACT > 0 ? layer - 1 : 0][a][ks];
+    };
+    auto stage_hidden = [&](int layer, h8 (&hT)[4]) {
 #pragma unroll
-      for (int r = 0; r < 4; ++r) {
-        dyT[r] = f2h(t0[r]);
-        dyT[4 + r] = f2h(t1[r]);
-      }
-    }
+      for (int a = 0; a < 2; ++a)
+#pragma unroll
+        for (int ks = 0; ks < 2; ++ks) stage_write<SG::PITCH>(stage_wr, a, ks, hid(layer, a, ks));
+#pragma unroll
+      for (int nt = 0; nt < 4; ++nt) hT[nt] = stage_read_t<SG::PITCH>(stage_rd, nt);
+      asm volatile("" ::: "memory");
+    };
+    h8 xTn;  // the next column tile's xT, read while the current one's dW1 MFMAs run
+    auto stage_x = [&]() {
+#pragma unroll
+      for (int a = 0; a < 2; ++a)
+#pragma unroll
+        for (int ks = XKS_LO; ks < XKS_HI; ++ks) stage_write<SG::PITCH>(stage_wr, a, ks - XKS_LO, cur.x[a][ks]);
+      xTn = stage_read_t<SG::PITCH>(stage_rd, COL_LO - 2 * XKS_LO);
+      asm volatile("" ::: "memory");
+    };
+    // pin_after / pin_behind: an empty asm on an MFMA operand = its last definition.  MFMAs are no memory operations, so the
+    // barriers do not hold them: left alone the scheduler moves the dW MFMAs of a section in front of the chain MFMAs that are
+    // there to cover their operands' round trip (and then waits for the reads right behind their request).  pin_behind ties the
+    // operand to a value the chain produces, pin_after to the position behind a group of requests.
+    typedef uint32_t PinU4 __attribute__((ext_vector_type(4)));
+    auto pin_after = [&](h8& v) { asm volatile("" : "+v"(reinterpret_cast<PinU4&>(v))); };
+    auto pin_behind = [&](h8& v, const h8& dep) { asm volatile("" : "+v"(reinterpret_cast<PinU4&>(v)) : "v"(reinterpret_cast<const PinU4&>(dep))); };
+    // the gated dZ of a hidden layer (chain layout, as the next layer's B operand needs it) -> batch-major.  An image of its own
+    // (second half of the region): x's image is already in place while the last hidden layer's dZ passes through.
+    auto stage_dz = [&](const h8 (&nz)[2][2], h8 (&zT)[4]) {
+#pragma unroll
+      for (int a = 0; a < 2; ++a)
+#pragma unroll
+        for (int ks = 0; ks < 2; ++ks) stage_write<SG::PITCH>(stage_wr + SG::BYTES, a, ks, *reinterpret_cast<const uint4*>(&nz[a][ks]));
+#pragma unroll
+      for (int nt = 0; nt < 4; ++nt) zT[nt] = stage_read_t<SG::PITCH>(stage_rd + SG::BYTES, nt);
+      asm volatile("" ::: "memory");
+    };
+    // A section's chain weight fragments are requested AHEAD of the staging groups that precede its chain MFMAs: DS operations
+    // return in order, so fragments requested behind a group make the first chain MFMA wait for the whole group.
+    h8 wch[8];
+    auto preload_chain = [&](int base, int n) {
+#pragma unroll
+      for (int q = 0; q < 8; ++q)
+        if (q < n) wch[q] = FR(base + q);
+      asm volatile("" ::: "memory");
+#pragma unroll
+      for (int q = 0; q < 8; ++q)
+        if (q < n) asm volatile("" : "+v"(reinterpret_cast<PinU4&>(wch[q])));  // (the chain MFMAs stay behind ALL the requests)
+    };
+    preload_chain(L::WOT_P, 4);
+#pragma unroll
+    for (int a = 0; a < 2; ++a) stage_write<SG::PITCH>(stage_wr, a, 0, cur.dy[a]);  // (features 16 .. 31 of the image: the zeros of g >= 2)
+    dyT = stage_read_t<SG::PITCH>(stage_rd, 0);
+    asm volatile("" ::: "memory");
+    h8 hT[4];
+    stage_hidden(NH, hT);
+    if (NH == 1) stage_x();
     // activations of the last hidden layer, chain layout [a][ks]
     h8 hf[2][2];
-    if (RECOMP) {
 #pragma unroll
-      for (int a = 0; a < 2; ++a)
+    for (int a = 0; a < 2; ++a)
 #pragma unroll
-        for (int ks = 0; ks < 2; ++ks) hf[a][ks] = hrec[NH - 1][a][ks];
-    } else {
-#pragma unroll
-      for (int a = 0; a < 2; ++a)
-#pragma unroll
-        for (int ks = 0; ks < 2; ++ks) hf[a][ks] = *reinterpret_cast<h8*>(&cur.h[NACT > 0 ? NH - 1 : 0][a][ks]);
-    }
-    h8 hT[4];
-#pragma unroll
-    for (int nt = 0; nt < 4; ++nt) {
-      const h8 sel = (nt & 1) ? I1 : I0;
-      f4 t0 = MFMA(hf[0][nt >> 1], sel, (f4{0, 0, 0, 0}));
-      f4 t1 = MFMA(hf[1][nt >> 1], sel, (f4{0, 0, 0, 0}));
-#pragma unroll
-      for (int r = 0; r < 4; ++r) {
-        hT[nt][r] = f2h(t0[r]);
-        hT[nt][4 + r] = f2h(t1[r]);
+      for (int ks = 0; ks < 2; ++ks) {
+        const uint4 u = hid(NH, a, ks);
+        hf[a][ks] = *reinterpret_cast<const h8*>(&u);
       }
-      if (REST) dWo[nt] = MFMA(dyT, hT[nt], dWo[nt]);
-    }
-    // dH_NH (chain) and dH_NH' (orientation 2), masked by ReLU
+    // dH_NH, masked by ReLU (chain layout), and its batch-major copy out of the dZ image
     {
       h8 nz[2][2];
 #pragma unroll
@@ -578,7 +667,7 @@ __global__ void __launch_bounds__(256, (IN_TILES == 1 && NH <= 2 ? MLP_BWD_NARRO
         f4 c[4];
 #pragma unroll
         for (int mt = 0; mt < 4; ++mt) {
-          c[mt] = MFMA(FR(L::WOT_P + mt), dzf[a][0], (f4{0, 0, 0, 0}));
+          c[mt] = MFMA(wch[mt], dzf[a][0], (f4{0, 0, 0, 0}));
           if (!RELU_GATE_ASM) {
 #pragma unroll
             for (int r = 0; r < 4; ++r)
@@ -598,20 +687,13 @@ __global__ void __launch_bounds__(256, (IN_TILES == 1 && NH <= 2 ? MLP_BWD_NARRO
           }
         }
       }
+      if (REST) {
+        pin_behind(dyT, nz[1][1]);
 #pragma unroll
-      for (int nt = 0; nt < 4; ++nt) {
-        f4 t0 = MFMA(dzf[0][0], FR(L::WOT_N + nt), (f4{0, 0, 0, 0}));
-        f4 t1 = MFMA(dzf[1][0], FR(L::WOT_N + nt), (f4{0, 0, 0, 0}));
-        if (RELU_GATE_ASM) {
-          dzT[nt] = relu_gate(t0, t1, hT[nt]);
-        } else {
-#pragma unroll
-          for (int r = 0; r < 4; ++r) {
-            dzT[nt][r] = (hT[nt][r] > (half_t)0.0f) ? f2h_grad(t0[r]) : (half_t)0.0f;
-            dzT[nt][4 + r] = (hT[nt][4 + r] > (half_t)0.0f) ? f2h_grad(t1[r]) : (half_t)0.0f;
-          }
-        }
+        for (int nt = 0; nt < 4; ++nt) dWo[nt] = MFMA(dyT, hT[nt], dWo[nt]);
       }
+      if (NH > 1) preload_chain(L::WH, 8);
+      stage_dz(nz, dzT);  // (its round trip: behind the next section's reads and chain MFMAs)
 #pragma unroll
       for (int a = 0; a < 2; ++a)
 #pragma unroll
@@ -621,42 +703,24 @@ __global__ void __launch_bounds__(256, (IN_TILES == 1 && NH <= 2 ? MLP_BWD_NARRO
 #pragma unroll
     for (int li = 0; li < NH - 1; ++li) {
       const int layer = NH - li;  // current dZ belongs to hidden layer `layer`; its input is H_{layer-1}
+      stage_hidden(layer - 1, hT);
+      if (layer == 2) stage_x();
 #pragma unroll
       for (int a = 0; a < 2; ++a)
 #pragma unroll
         for (int ks = 0; ks < 2; ++ks) {
-          if (RECOMP) {
-            hf[a][ks] = hrec[RECOMP ? layer - 2 : 0][a][ks];
-          } else {
-            hf[a][ks] = *reinterpret_cast<h8*>(&cur.h[NACT > 0 ? layer - 2 : 0][a][ks]);
-          }
+          const uint4 u = hid(layer - 1, a, ks);
+          hf[a][ks] = *reinterpret_cast<const h8*>(&u);
         }
-#pragma unroll
-      for (int nt = 0; nt < 4; ++nt) {
-        const h8 sel = (nt & 1) ? I1 : I0;
-        f4 t0 = MFMA(hf[0][nt >> 1], sel, (f4{0, 0, 0, 0}));
-        f4 t1 = MFMA(hf[1][nt >> 1], sel, (f4{0, 0, 0, 0}));
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-          hT[nt][r] = f2h(t0[r]);
-          hT[nt][4 + r] = f2h(t1[r]);
-        }
-      }
-      if (REST) {
-#pragma unroll
-        for (int mt = 0; mt < 4; ++mt)
-#pragma unroll
-          for (int nt = 0; nt < 4; ++nt) dWh[layer - 2][mt][nt] = MFMA(dzT[mt], hT[nt], dWh[layer - 2][mt][nt]);
-      }
-      const int fb = L::WH + li * 16;
-      h8 nz[2][2], nzT[4];
+      const int fb = L::WH + li * 8;  // (this section's fragments fb .. fb + 7 are in wch: preload_chain)
+      h8 nz[2][2];
 #pragma unroll
       for (int a = 0; a < 2; ++a) {
         f4 c[4];
 #pragma unroll
         for (int mt = 0; mt < 4; ++mt) {
-          c[mt] = MFMA(FR(fb + mt * 2 + 0), dzf[a][0], (f4{0, 0, 0, 0}));
-          c[mt] = MFMA(FR(fb + mt * 2 + 1), dzf[a][1], c[mt]);
+          c[mt] = MFMA(wch[mt * 2 + 0], dzf[a][0], (f4{0, 0, 0, 0}));
+          c[mt] = MFMA(wch[mt * 2 + 1], dzf[a][1], c[mt]);
           if (!RELU_GATE_ASM) {
 #pragma unroll
             for (int r = 0; r < 4; ++r)
@@ -676,61 +740,57 @@ __global__ void __launch_bounds__(256, (IN_TILES == 1 && NH <= 2 ? MLP_BWD_NARRO
           }
         }
       }
+      if (REST) {
 #pragma unroll
-      for (int nt = 0; nt < 4; ++nt) {
-        f4 t0 = MFMA(dzf[0][0], FR(fb + 8 + nt * 2 + 0), (f4{0, 0, 0, 0}));
-        t0 = MFMA(dzf[0][1], FR(fb + 8 + nt * 2 + 1), t0);
-        f4 t1 = MFMA(dzf[1][0], FR(fb + 8 + nt * 2 + 0), (f4{0, 0, 0, 0}));
-        t1 = MFMA(dzf[1][1], FR(fb + 8 + nt * 2 + 1), t1);
-        if (RELU_GATE_ASM) {
-          nzT[nt] = relu_gate(t0, t1, hT[nt]);
-        } else {
+        for (int nt = 0; nt < 4; ++nt) pin_behind(hT[nt], nz[1][1]);
 #pragma unroll
-          for (int r = 0; r < 4; ++r) {
-            nzT[nt][r] = (hT[nt][r] > (half_t)0.0f) ? f2h_grad(t0[r]) : (half_t)0.0f;
-            nzT[nt][4 + r] = (hT[nt][4 + r] > (half_t)0.0f) ? f2h_grad(t1[r]) : (half_t)0.0f;
-          }
-        }
+        for (int mt = 0; mt < 4; ++mt)
+#pragma unroll
+          for (int nt = 0; nt < 4; ++nt) dWh[layer - 2][mt][nt] = MFMA(dzT[mt], hT[nt], dWh[layer - 2][mt][nt]);
       }
+      if (layer > 2) preload_chain(fb + 8, 8);
+      stage_dz(nz, dzT);  // (dzT's last use is just above; round trip: behind the next section's reads and chain MFMAs)
 #pragma unroll
       for (int a = 0; a < 2; ++a)
 #pragma unroll
         for (int ks = 0; ks < 2; ++ks) dzf[a][ks] = nz[a][ks];
-#pragma unroll
-      for (int nt = 0; nt < 4; ++nt) dzT[nt] = nzT[nt];
     }
     // ---- first layer: dW1 = dZ1^T X, dX = dZ1 W1 ---------------------------------------------
     {
-      if (!RECOMP) {
+      // dX's weight fragments (W1^T, natural rows), where they are few (the condition of PIN_NEXT): requested here, behind the first
+      // xT, so that their round trip passes under the dW1 MFMAs instead of in front of each dX MFMA; once for both chain tiles.
+      constexpr bool DX_PRELOAD = (COL_HI - DX_LO) <= 2;
+      h8 wdx[DX_PRELOAD ? 2 * (COL_HI - DX_LO) : 1];
+      if (DX_PRELOAD && (dx || ATTR_EPI)) {
 #pragma unroll
-        for (int a = 0; a < 2; ++a)
-#pragma unroll
-          for (int ks = 0; ks < KS_IN; ++ks) xf[a][ks] = *reinterpret_cast<h8*>(&cur.x[a][ks]);
+        for (int q = 0; q < 2 * (COL_HI - DX_LO); ++q) wdx[q] = FR(L::W1T + 2 * DX_LO + q);
+        asm volatile("" ::: "memory");
       }
 #pragma unroll
       for (int nt = COL_LO; nt < COL_HI; ++nt) {
-        const h8 sel = (nt & 1) ? I1 : I0;
-        f4 t0 = MFMA(xf[0][nt >> 1], sel, (f4{0, 0, 0, 0}));
-        f4 t1 = MFMA(xf[1][nt >> 1], sel, (f4{0, 0, 0, 0}));
-        h8 xT;
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-          xT[r] = f2h(t0[r]);
-          xT[4 + r] = f2h(t1[r]);
+        h8 xT = xTn;
+        if (nt + 1 < COL_HI) {
+          xTn = stage_read_t<SG::PITCH>(stage_rd, nt + 1 - 2 * XKS_LO);
+          asm volatile("" ::: "memory");
+          pin_after(xT);
         }
 #pragma unroll
         for (int mt = 0; mt < 4; ++mt) dW1[mt][nt - COL_LO] = MFMA(dzT[mt], xT, dW1[mt][nt - COL_LO]);
       }
       if (PIN_NEXT) pin_tile(nxt, ent_nn);  // the NEXT tile's inputs are taken over here, in front of this tile's dX stores (see pin_tile)
       if (dx || ATTR_EPI) {
+        if (DX_PRELOAD) {
+#pragma unroll
+          for (int q = 0; q < 2 * (COL_HI - DX_LO); ++q) pin_after(wdx[q]);  // (the dX MFMAs stay behind the dW1 loop)
+        }
         constexpr int DX_PITCH = DX_LO == COL_LO ? IN_PAD : (COL_HI - DX_LO) * 16;  // full rows, or only the tiles from DX_LO on
         constexpr int DX_T0 = DX_LO == COL_LO ? 0 : DX_LO;
 #pragma unroll
         for (int a = 0; a < 2; ++a)
 #pragma unroll
           for (int mt = DX_LO; mt < COL_HI; ++mt) {
-            f4 c = MFMA(FR(L::W1T + mt * 2 + 0), dzf[a][0], (f4{0, 0, 0, 0}));
-            c = MFMA(FR(L::W1T + mt * 2 + 1), dzf[a][1], c);
+            f4 c = MFMA(DX_PRELOAD ? wdx[DX_PRELOAD ? 2 * (mt - DX_LO) + 0 : 0] : FR(L::W1T + mt * 2 + 0), dzf[a][0], (f4{0, 0, 0, 0}));
+            c = MFMA(DX_PRELOAD ? wdx[DX_PRELOAD ? 2 * (mt - DX_LO) + 1 : 0] : FR(L::W1T + mt * 2 + 1), dzf[a][1], c);
             if (ok[a]) {
               h4 ov;
 #pragma unroll

@@ -41,12 +41,42 @@ __device__ __forceinline__ h8 build_frag(const half_t* __restrict__ W, int R, in
   return v;
 }
 
-__device__ __forceinline__ h8 ident_frag(int lane, int half_sel) {
-  const int j = lane & 15, g = lane >> 4;
-  h8 v;
-#pragma unroll
-  for (int e = 0; e < 8; ++e) v[e] = (8 * g + e == 16 * half_sel + j) ? (half_t)1.0f : (half_t)0.0f;
-  return v;
+// ---- wave-private LDS staging image of the backward kernel (mlp.hip header comment: "Backward") -------------------------
+// One [32 rows][32 NKS features] fp16 image per wavefront, written from the chain layout (lane (i, g) holds 8 consecutive features
+// of macro-tile row R = 8 (i >> 2) + 4 a + (i & 3)) with ds_write_b128 and read back batch-major with ds_read_b64_tr_b16.
+//   byte address of (R, feature c) = (R >> 3) BLK + (R & 7) PITCH + 2 c,   PITCH = 32 (2 NKS + 1),   BLK = 8 PITCH + 128
+// Banks: a transposed read is served per 32-lane half = row blocks g, g + 1 x rows q = 0 .. 3 x 32 contiguous bytes, at
+// 128 g + 32 (q (2 NKS + 1) mod 8) (mod 256): with PITCH an ODD multiple of 32 bytes and BLK = 128 (mod 256) these are the eight
+// distinct 32-byte slots of the 256-byte bank row -- no conflict (predicted degree 1).  A ds_write_b128 is served per 8 consecutive
+// lanes (128-byte bank row for stores) = rows 0 .. 3 of two row blocks at one feature offset: BLK = 0 (mod 128) puts the two blocks
+// on the same banks -- degree 2, 16 LDS cycles against the 13 the instruction takes to move its registers anyway.
+// Every address is a multiple of 8 (reads) / 16 (writes) as long as the region's base is a multiple of 16.
+template <int NKS>
+struct BwdStage {
+  static constexpr int PITCH = 32 * (2 * NKS + 1);
+  static constexpr int BLK = 8 * PITCH + 128;
+  static constexpr int BYTES = 4 * BLK;
+};
+typedef __attribute__((address_space(3))) unsigned char lds_u8;
+// this lane's 16 bytes (row of chain tile a, features 32 ks + 8 g ..) -> image; wr = region + (i >> 2) BLK + (i & 3) PITCH + 16 g
+template <int PITCH>
+__device__ __forceinline__ void stage_write(lds_u8* wr, int a, int ks, const uint4& v) {
+  typedef uint32_t U4 __attribute__((ext_vector_type(4)));
+  *reinterpret_cast<__attribute__((address_space(3))) U4*>(wr + 4 * a * PITCH + 64 * ks) = U4{v.x, v.y, v.z, v.w};
+}
+// rows 8 g .. 8 g + 7 of feature 16 nt + i: the B operand (and, as dZ, the A operand) of a batch contraction.  rd = region + g BLK +
+// (i >> 2) PITCH + 8 (i & 3): lane 4 q + p of a 16-lane group addresses row q, columns 4 p .. 4 p + 3 of the group's 4 x 16 block and
+// receives column i.  MUST run with EXEC all ones (masked lanes' addresses still take part): only in wave-uniform control flow.
+template <int PITCH>
+__device__ __forceinline__ h8 stage_read_t(lds_u8* rd, int nt) {
+  typedef __fp16 tr_h4 __attribute__((__vector_size__(8)));
+  typedef __attribute__((address_space(3))) tr_h4 lds_tr_h4;
+  const tr_h4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4f16(reinterpret_cast<lds_tr_h4*>(rd + 32 * nt));
+  const tr_h4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4f16(reinterpret_cast<lds_tr_h4*>(rd + 4 * PITCH + 32 * nt));
+  h8 out;
+  __builtin_memcpy(&out, &lo, 8);
+  __builtin_memcpy(reinterpret_cast<char*>(&out) + 8, &hi, 8);
+  return out;
 }
 
 __device__ __forceinline__ h8 relu_pack(const f4& lo, const f4& hi) {
