@@ -1,6 +1,6 @@
 """Scene-flow field.  Mirror of the reference's model/flow_field.py:40-130 (``FlowField`` with use_grid=True,
 use_freq=False): 3-D hash grid (8 levels x 8 features) -> interpT over feature chunks -> bias-free ReLU MLP
-16 -> 64 -> 64 -> 6.  State-dict keys ``grid_enc.params``, ``mlp.{0,2,4}.weight`` as in the reference.
+16 -> 64 -> 64 -> 6 (hidden width 16, 32, 64 or 128).  State-dict keys ``grid_enc.params``, ``mlp.{0,2,4}.weight`` as in the reference.
 
 Two launches: grid lookup + interpT fused (l4d_hashgrid_t_fwd with one table), then the MFMA MLP (l4d_mlp_fwd)
 with the fp16-operand / fp32-accumulate numerics the reference's autocast run gives its nn.Linear layers.
@@ -20,7 +20,7 @@ class _FlowFn(torch.autograd.Function):
         t_dev = xt_c[0, 3:4]
         xf = ops.hashgrid_t_fwd(mod.grid_enc.meta, xt_c, (0, 1, 2), [mod.grid_enc._half_params()], t_dev, half_out=True)
         w16 = mod._weights16()
-        y, act = ops.mlp_fwd(xf, w16, mod.n_hidden, save_act=True)
+        y, act = ops.mlp_fwd(xf, w16, mod.n_hidden, save_act=True, hidden=mod.hidden_dim)
         ctx.mod = mod
         ctx.save_for_backward(xt_c, xf, act, w16)
         # fp32 tensor holding the fp16-rounded outputs (same values as the reference's autocast nn.Linear): autograd hands a
@@ -46,7 +46,7 @@ class _FlowFn(torch.autograd.Function):
         dy16 = torch.zeros(P, 16, dtype=torch.float16, device=dy.device)
         dy16[:, :6] = dyf * s
         gw = torch.zeros(w16.numel(), dtype=torch.float32, device=dy.device)
-        dxf = ops.mlp_bwd(xf, act, dy16, w16, mod.n_hidden, gw, 1.0)
+        dxf = ops.mlp_bwd(xf, act, dy16, w16, mod.n_hidden, gw, 1.0, hidden=mod.hidden_dim)
         ggrid = torch.zeros_like(mod.grid_enc.params)
         ops.hashgrid_t_bwd(mod.grid_enc.meta, xt_c, (0, 1, 2), 1, xt_c[0, 3:4], dxf, [ggrid], 1.0)
         ggrid *= inv
@@ -59,9 +59,9 @@ class FlowField(nn.Module):
                  num_basis=4, n_levels=8, n_features_per_level=8, base_resolution=32, max_resolution=8192,
                  log2_hashmap_size=18):
         super().__init__()
-        if use_freq or not use_grid or num_basis != 4 or n_features_per_level != 8 or hidden_dim != 64:
+        if use_freq or not use_grid or num_basis != 4 or n_features_per_level != 8 or hidden_dim not in (16, 32, 64, 128):
             raise ValueError("FlowField: only the reference configuration (grid encoding, 8 features/level, "
-                             "num_basis 4, hidden 64) is implemented")
+                             "num_basis 4, hidden 16 / 32 / 64 / 128) is implemented")
         if not 2 <= num_layers <= 4:
             raise ValueError("FlowField: 2..4 layers supported")
         self.use_freq, self.use_grid = use_freq, use_grid
@@ -84,16 +84,18 @@ class FlowField(nn.Module):
         self.mlp = nn.Sequential(*layers)
         torch.nn.init.normal_(self.mlp[-1].weight.data, 0, 0.001)
         self.n_hidden = num_layers - 1
+        self.hidden_dim = hidden_dim
         self.loss_scale = 128.0
 
     def linears(self):
         return [m for m in self.mlp if isinstance(m, nn.Linear)]
 
     def weight_numel16(self):
-        return 64 * self.input_dim + (self.n_hidden - 1) * 64 * 64 + 16 * 64
+        h = self.hidden_dim
+        return h * self.input_dim + (self.n_hidden - 1) * h * h + 16 * h
 
     def _weights16(self, out=None):
-        """fp16 weights in the MLP kernel's layout: [64,in], (n_hidden-1) x [64,64], [16,64] (6 real rows)."""
+        """fp16 weights in the MLP kernel's layout: [h,in], (n_hidden-1) x [h,h], [16,h] (6 real rows), h = hidden_dim."""
         lins = self.linears()
         if out is None:
             out = torch.zeros(self.weight_numel16(), dtype=torch.float16, device=lins[0].weight.device)
@@ -102,7 +104,7 @@ class FlowField(nn.Module):
             n = m.weight.numel()
             out[off:off + n] = m.weight.detach().reshape(-1)
             off += n
-        out[off:off + 6 * 64] = lins[-1].weight.detach().reshape(-1)
+        out[off:off + 6 * self.hidden_dim] = lins[-1].weight.detach().reshape(-1)
         return out
 
     def _split_weight_grads(self, gw):
@@ -112,7 +114,7 @@ class FlowField(nn.Module):
             n = m.weight.numel()
             grads.append(gw[off:off + n].view_as(m.weight))
             off += n
-        grads.append(gw[off:off + 6 * 64].view_as(lins[-1].weight))
+        grads.append(gw[off:off + 6 * self.hidden_dim].view_as(lins[-1].weight))
         return grads
 
     def forward(self, xt):

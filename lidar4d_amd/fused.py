@@ -113,15 +113,20 @@ class RenderFn(torch.autograd.Function):
         fn = model.flow_net
         xf = ops.hashgrid_t_fwd(fn.grid_enc.meta, xt, (0, 1, 2), [store.half(fn.grid_enc.params)], t_dev, half_out=True)
         # hidden activations are only stored where the backward cannot recompute them from the input rows (ops.mlp_recompute_supported)
-        flow16, act_f = ops.mlp_fwd(xf, _flow_w16(model), fn.n_hidden, save_act=train and not ops.mlp_recompute_supported(xf.shape[1], fn.n_hidden))
+        flow16, act_f = ops.mlp_fwd(xf, _flow_w16(model), fn.n_hidden, hidden=fn.hidden_dim,
+                                    save_act=train and not ops.mlp_recompute_supported(xf.shape[1], fn.n_hidden, fn.hidden_dim))
 
         # density (lidar4d.py:139-188)
         fd = _field_desc(model)
         # ... and the density network with its activation (trunc_exp, activation.py:6-20) in the same call: for the default shape it
         # runs as the encode kernel's epilogue on the rows in LDS (csrc/fused.hip SIGMA)
         sn = model.sigma_net
-        X, h, act_s, sigma = ops.density_encode_fwd(fd, xt, flow16, tinfo, sn.in_pad, sigma_weights16=store.half(sn.params), n_hidden=sn.n_hidden_layers,
-                                                    save_act=train and not ops.mlp_recompute_supported(sn.in_pad, sn.n_hidden_layers))
+        if sn.n_neurons == 64:
+            X, h, act_s, sigma = ops.density_encode_fwd(fd, xt, flow16, tinfo, sn.in_pad, sigma_weights16=store.half(sn.params), n_hidden=sn.n_hidden_layers,
+                                                        save_act=train and not ops.mlp_recompute_supported(sn.in_pad, sn.n_hidden_layers))
+        else:  # another width: the rows, then the width-generic network with the same epilogue (un-fused)
+            X = ops.density_encode_fwd(fd, xt, flow16, tinfo, sn.in_pad)
+            h, act_s, sigma = ops.mlp_fwd_sigma(X, store.half(sn.params), sn.n_hidden_layers, save_act=train, hidden=sn.n_neurons)
 
         # compositing + mask compaction (renderer.py:98-110)
         weights, wsum, depth, _, idx, count = ops.composite_fwd(sigma, z_vals, sample_dist, model.density_scale,
@@ -130,7 +135,7 @@ class RenderFn(torch.autograd.Function):
         # attribute (lidar4d.py:191-223) on the compacted work list
         denc = ops.freq_fwd(((rays_d + 1) / 2).contiguous(), model.view_encoder.n_frequencies)
         an = model.intensity_net
-        gathered = ops.attr_mlp_supported(an.in_pad, denc.shape[1], model.geo_feat_dim)
+        gathered = ops.attr_mlp_supported(an.in_pad, denc.shape[1], model.geo_feat_dim) and an.n_neurons == 64
         attr = torch.zeros(P, 2, dtype=torch.float32, device=dev)
         attr_c = torch.empty(P, 2, dtype=torch.float32, device=dev)
         if gathered:  # the networks assemble their input rows themselves, forward and backward (three hidden layers: the first
@@ -145,8 +150,8 @@ class RenderFn(torch.autograd.Function):
                                        an.n_hidden_layers, save_act=keep_act, attr_dense=attr, attr_compact=attr_c, channel=1)
         else:
             XA = ops.attr_gather(idx, count, P, T, denc, h, model.geo_feat_dim, an.in_pad)
-            yR, actR = ops.mlp_fwd(XA, store.half(model.raydrop_net.params), an.n_hidden_layers, save_act=train, n_rows=count)
-            yI, actI = ops.mlp_fwd(XA, store.half(model.intensity_net.params), an.n_hidden_layers, save_act=train, n_rows=count)
+            yR, actR = ops.mlp_fwd(XA, store.half(model.raydrop_net.params), an.n_hidden_layers, save_act=train, n_rows=count, hidden=an.n_neurons)
+            yI, actI = ops.mlp_fwd(XA, store.half(model.intensity_net.params), an.n_hidden_layers, save_act=train, n_rows=count, hidden=an.n_neurons)
             ops.attr_scatter(idx, count, P, yR, yI, attr, attr_c)
         image = ops.composite_image(weights, attr, 2)
 
@@ -208,9 +213,9 @@ class RenderFn(torch.autograd.Function):
                 ops.attr_gather_bwd(idx, count, P, dxaR, dxaI, an.in_pad - 64, n_enc - 64, model.geo_feat_dim, dh, h_layout=True)
             else:
                 dxaR = ops.mlp_bwd(XA, actR, dyR, store.half(model.raydrop_net.params), an.n_hidden_layers,
-                                   store.grad_view(model.raydrop_net.params), inv, n_rows=count)
+                                   store.grad_view(model.raydrop_net.params), inv, n_rows=count, hidden=an.n_neurons)
                 dxaI = ops.mlp_bwd(XA, actI, dyI, store.half(model.intensity_net.params), an.n_hidden_layers,
-                                   store.grad_view(model.intensity_net.params), inv, n_rows=count)
+                                   store.grad_view(model.intensity_net.params), inv, n_rows=count, hidden=an.n_neurons)
                 ops.attr_gather_bwd(idx, count, P, dxaR, dxaI, an.in_pad, n_enc, model.geo_feat_dim, dh)
         if not sigma_done:
             ops.sigma_bwd(h, d_sigma.view(-1), ls, dh)
@@ -223,7 +228,8 @@ class RenderFn(torch.autograd.Function):
         n_pl = pe.layout.n_scales * pe.layout.C
         gd_absmax = torch.zeros(1, dtype=torch.float32, device=dev) if n_pl % 16 == 0 else None  # (rows wider than 128: two launches, each reports the tiles it stores)
         dX = ops.mlp_bwd(X, act_s, dh, store.half(model.sigma_net.params), model.sigma_net.n_hidden_layers,
-                         store.grad_view(model.sigma_net.params), inv, dx_absmax=gd_absmax, absmax_cols=(n_pl, 2 * n_pl))
+                         store.grad_view(model.sigma_net.params), inv, dx_absmax=gd_absmax, absmax_cols=(n_pl, 2 * n_pl),
+                         hidden=model.sigma_net.n_neurons)
         # field
         gcl = torch.zeros(pe.layout.numel, dtype=torch.float32, device=dev)
         fd = _field_desc(model)
@@ -238,7 +244,7 @@ class RenderFn(torch.autograd.Function):
             hook()
         # flow network + grid
         fn = model.flow_net
-        dxf = ops.mlp_bwd(xf, act_f, dflow16, _flow_w16(model), fn.n_hidden, _flow_wgrad(model), inv)
+        dxf = ops.mlp_bwd(xf, act_f, dflow16, _flow_w16(model), fn.n_hidden, _flow_wgrad(model), inv, hidden=fn.hidden_dim)
         ops.hashgrid_t_bwd(fn.grid_enc.meta, xt, (0, 1, 2), 1, t_dev, dxf, [store.grad_view(fn.grid_enc.params)], inv)
         pair = ctx.slice_pair
         if pair is not None:  # reference semantics for a torch optimiser: untouched slices keep .grad = None (LiDAR4D.run)

@@ -81,7 +81,7 @@ class LiDAR4D(LiDAR_Renderer):
         g1 = (named(self.flow_net, "flow_net.") + named(self.sigma_net, "sigma_net.") +
               named(self.intensity_net, "intensity_net.") + named(self.raydrop_net, "raydrop_net."))
         last = "flow_net.mlp.%d.weight" % (len(self.flow_net.mlp) - 1)
-        object.__setattr__(self, "_store", ParamStore([g0, g1], pad_to={last: 16 * 64}))
+        object.__setattr__(self, "_store", ParamStore([g0, g1], pad_to={last: 16 * self.flow_net.hidden_dim}))
         for m in self.modules():
             if isinstance(m, (tcnn.HashGridEncoding, tcnn.FullyFusedMLP)):
                 object.__setattr__(m, "_store", self._store)

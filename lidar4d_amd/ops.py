@@ -187,24 +187,40 @@ def freq_fwd(x, n_freq=12, out=None):
     return out
 
 
-def mlp_fwd(x16, weights16, n_hidden, save_act=True, n_rows=None, y=None, act=None):
-    """x16 [P, in_pad] fp16 -> y [P,16] fp16 (+ act [n_hidden, P, 64] fp16)."""
+def _mlp_width_call(name, *args):
+    """The widths other than 64: liblidar4d_mlp.so (include/lidar4d_mlp.h), mapped on first use."""
+    from . import _mlp_lib
+    _mlp_lib.call(name, *args)
+
+
+def mlp_fwd(x16, weights16, n_hidden, save_act=True, n_rows=None, y=None, act=None, hidden=64, sigma=None):
+    """x16 [P, in_pad] fp16 -> y [P,16] fp16 (+ act [n_hidden, P, hidden] fp16).  hidden: the network's width, 16 / 32 / 64 / 128.
+    sigma ([P] fp32, only for hidden != 64): receives exp(y[:, 0]), the density activation, as epilogue."""
     _chk(x16, torch.float16, "x"), _chk(weights16, torch.float16, "weights"), _chk(n_rows, torch.int32, "n_rows")
     P, in_pad = x16.shape
     if y is None:
         y = torch.empty(P, 16, dtype=torch.float16, device=x16.device)
     if save_act and act is None:
-        act = torch.empty(n_hidden, P, 64, dtype=torch.float16, device=x16.device)
+        act = torch.empty(n_hidden, P, hidden, dtype=torch.float16, device=x16.device)
+    if hidden != 64:
+        _chk(sigma, torch.float32, "sigma")
+        _mlp_width_call("l4dm_mlp_fwd", _p(x16), P, _p(n_rows), in_pad, hidden, n_hidden, _p(weights16), _p(y), _p(act), _p(sigma),
+                        _stream())
+        return y, act
+    if sigma is not None:
+        raise ValueError("mlp_fwd: the sigma epilogue of width 64 is mlp_fwd_sigma")
     call("l4d_mlp_fwd", _p(x16), P, _p(n_rows), in_pad, n_hidden, _p(weights16), _p(y), _p(act), _stream())
     return y, act
 
 
-def mlp_recompute_supported(in_pad, n_hidden):
+def mlp_recompute_supported(in_pad, n_hidden, hidden=64):
     """Shapes for which l4d_mlp_bwd recomputes the hidden activations itself (act = None), so that the forward does not store
     them: narrow inputs (the flow network: 32-byte rows against 256 B of activations; measured forward 1.11 -> 0.33 ms,
     backward 1.64 -> 1.41 ms at 12.6 M rows) and, since round 5, the 128 -> 64 -> 16 density network (round 2 had measured that
     trade neutral, forward 0.91 -> 0.67 ms, backward 1.93 -> 2.13 ms; with today's kernels it is -0.17 ms per step).  Wider / deeper
-    shapes spill registers and keep their activations."""
+    shapes spill registers and keep their activations.  Widths other than 64 always keep them."""
+    if hidden != 64:
+        return False
     if in_pad == 128 and n_hidden == 1:
         # the density network (round 5): its forward runs as the encode kernel's epilogue and stores 128 B less per sample, the backward
         # reads 128 B less and recomputes the hidden layer from the row it reads anyway: 32.08 -> 31.91 ms per step (gpurun_out/s6;
@@ -214,7 +230,7 @@ def mlp_recompute_supported(in_pad, n_hidden):
 
 
 def mlp_bwd(x16, act, dy16, weights16, n_hidden, grad_w, inv_loss_scale, n_rows=None, want_dx=True, dx=None, dx_absmax=None,
-            absmax_cols=(0, 0)):
+            absmax_cols=(0, 0), hidden=64):
     """dx_absmax: 1-element fp32 device tensor (zeroed by the caller) that receives max |dx[:, absmax_cols[0]:absmax_cols[1]]|
     (columns in multiples of 16; +inf if a value is not finite)."""
     _chk(x16, torch.float16, "x"), _chk(act, torch.float16, "act"), _chk(dy16, torch.float16, "dy")
@@ -223,6 +239,12 @@ def mlp_bwd(x16, act, dy16, weights16, n_hidden, grad_w, inv_loss_scale, n_rows=
     P, in_pad = x16.shape
     if want_dx and dx is None:
         dx = torch.empty(P, in_pad, dtype=torch.float16, device=x16.device)
+    if hidden != 64:
+        if act is None:
+            raise ValueError("mlp_bwd: widths other than 64 need the stored activations (no recompute variant)")
+        _mlp_width_call("l4dm_mlp_bwd", _p(x16), _p(act), _p(dy16), P, _p(n_rows), in_pad, hidden, n_hidden, _p(weights16), _p(dx),
+                        _p(grad_w), float(inv_loss_scale), _p(dx_absmax), int(absmax_cols[0]), int(absmax_cols[1]), _stream())
+        return dx
     call("l4d_mlp_bwd", _p(x16), _p(act), _p(dy16), P, _p(n_rows), in_pad, n_hidden, _p(weights16), _p(dx), _p(grad_w),
          float(inv_loss_scale), _p(dx_absmax), int(absmax_cols[0]), int(absmax_cols[1]), _stream())
     return dx
@@ -317,10 +339,14 @@ def attr_mlp_fwd(idx, count, cap, T, dir_enc16, h16, n_geo, in_pad, weights16, n
     return y, act
 
 
-def mlp_fwd_sigma(x16, weights16, n_hidden, save_act=True):
+def mlp_fwd_sigma(x16, weights16, n_hidden, save_act=True, hidden=64):
     """mlp_fwd + the density activation as epilogue -> (y [P,16] fp16, act, sigma [P] fp32 = exp(y[:, 0]))."""
     _chk(x16, torch.float16, "x"), _chk(weights16, torch.float16, "weights")
     P, in_pad = x16.shape
+    if hidden != 64:
+        sigma = torch.empty(P, dtype=torch.float32, device=x16.device)
+        y, act = mlp_fwd(x16, weights16, n_hidden, save_act=save_act, hidden=hidden, sigma=sigma)
+        return y, act, sigma
     y = torch.empty(P, 16, dtype=torch.float16, device=x16.device)
     act = torch.empty(n_hidden, P, 64, dtype=torch.float16, device=x16.device) if save_act else None
     sigma = torch.empty(P, dtype=torch.float32, device=x16.device)

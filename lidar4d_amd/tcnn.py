@@ -101,7 +101,7 @@ class _MLPFn(torch.autograd.Function):
         P = x.shape[0]
         x16 = torch.ones(P, mod.in_pad, dtype=torch.float16, device=x.device)
         x16[:, : mod.n_input_dims] = x.detach()
-        y, act = ops.mlp_fwd(x16, mod._half_params(), mod.n_hidden_layers, save_act=True)
+        y, act = ops.mlp_fwd(x16, mod._half_params(), mod.n_hidden_layers, save_act=True, hidden=mod.n_neurons)
         ctx.mod = mod
         ctx.save_for_backward(x16, act)
         ctx.x_dtype = x.dtype
@@ -116,24 +116,25 @@ class _MLPFn(torch.autograd.Function):
         dy16 = torch.zeros(P, 16, dtype=torch.float16, device=dy.device)
         dy16[:, : mod.n_output_dims] = dy.float() * s  # not saturated: an overflow becomes inf and reaches the scaler (csrc/common.h f2h_grad)
         grad = torch.zeros_like(mod.params)
-        dx16 = ops.mlp_bwd(x16, act, dy16, mod._half_params(), mod.n_hidden_layers, grad, 1.0 / s)
+        dx16 = ops.mlp_bwd(x16, act, dy16, mod._half_params(), mod.n_hidden_layers, grad, 1.0 / s, hidden=mod.n_neurons)
         dx = (dx16[:, : mod.n_input_dims].float() / s).to(ctx.x_dtype)
         return dx, grad, None
 
 
 class FullyFusedMLP(nn.Module, _HalfParams):
-    """``otype: FullyFusedMLP``: bias-free, ReLU hidden layers of width 64, no output activation; the input is
+    """``otype: FullyFusedMLP``: bias-free, ReLU hidden layers of width 16, 32, 64 or 128, no output activation; the input is
     padded to a multiple of 16 with the constant 1.0, the output to 16."""
 
     def __init__(self, n_input_dims, n_output_dims, cfg, seed=1337):
         super().__init__()
         if cfg.get("activation", "ReLU") != "ReLU" or cfg.get("output_activation", "None") != "None":
             raise ValueError("lidar4d_amd.tcnn.Network: only ReLU / no output activation (what LiDAR4D configures)")
-        if int(cfg["n_neurons"]) != 64 or n_output_dims > 16:
-            raise ValueError("lidar4d_amd.tcnn.Network: n_neurons must be 64 and n_output_dims <= 16")
+        self.n_neurons = int(cfg["n_neurons"])
+        if self.n_neurons not in (16, 32, 64, 128) or n_output_dims > 16:
+            raise ValueError("lidar4d_amd.tcnn.Network: n_neurons must be 16, 32, 64 or 128 and n_output_dims <= 16")
         self.n_input_dims, self.n_output_dims = n_input_dims, n_output_dims
         self.n_hidden_layers = int(cfg["n_hidden_layers"])
-        self.shapes = mlp_layer_shapes(n_input_dims, n_output_dims, 64, self.n_hidden_layers)
+        self.shapes = mlp_layer_shapes(n_input_dims, n_output_dims, self.n_neurons, self.n_hidden_layers)
         self.in_pad = self.shapes[0][1]
         if self.in_pad not in (16, 32, 64, 96, 128, 160, 176, 192) or not 1 <= self.n_hidden_layers <= 3:
             raise ValueError("lidar4d_amd.tcnn.Network: padded input width in {16,32,64,96,128,160,176,192} and 1..3 "

@@ -445,12 +445,12 @@ class _SceneFlowLossFn(torch.autograd.Function):
         from .fused import _flow_w16
         store, fn, dev = model._store, model.flow_net, pc.device
         w16, grid16 = _flow_w16(model), store.half(fn.grid_enc.params)
-        keep_act = not ops.mlp_recompute_supported(fn.input_dim, fn.n_hidden)
+        keep_act = not ops.mlp_recompute_supported(fn.input_dim, fn.n_hidden, fn.hidden_dim)
 
         def evaluate(points, t):
             xt = ops.flow_xt(points, t, model.bound)
             xf = ops.hashgrid_t_fwd(fn.grid_enc.meta, xt, (0, 1, 2), [grid16], xt[0, 3:4], half_out=True)
-            y, act = ops.mlp_fwd(xf, w16, fn.n_hidden, save_act=keep_act)
+            y, act = ops.mlp_fwd(xf, w16, fn.n_hidden, save_act=keep_act, hidden=fn.hidden_dim)
             return xt, xf, act, y
 
         n = pc.shape[0]
@@ -505,7 +505,7 @@ class _SceneFlowLossFn(torch.autograd.Function):
             # buffers (sparse: most entries stay zero), then y += inv * x into the arena
             gw = torch.zeros(w16.numel(), dtype=torch.float32, device=dev)
             ggrid = torch.zeros(g_grid.numel(), dtype=torch.float32, device=dev)
-            dxf = ops.mlp_bwd(xf, act, dy16, w16, fn.n_hidden, gw, 1.0)
+            dxf = ops.mlp_bwd(xf, act, dy16, w16, fn.n_hidden, gw, 1.0, hidden=fn.hidden_dim)
             ops.hashgrid_t_bwd(fn.grid_enc.meta, xt, (0, 1, 2), 1, xt[0, 3:4], dxf, [ggrid], 1.0)
             pending = getattr(model, "_flow_loss_pending", None)
             if pending is not None:  # (Trainer with the scene-flow term on a side stream: added to the arena once the render path's own
