@@ -94,6 +94,13 @@ static int seg_for(int n, int m, int b) {
 
 extern "C" int64_t l4d_chamfer_workspace(int32_t b, int32_t n, int32_t m) { return (int64_t)b * ((int64_t)n + m) * 8; }
 
+// dist1 [b,n] / idx1 [b,n]: squared distance to and index of the nearest point of xyz2 for every point of xyz1; dist2 / idx2 the
+// other way round.  d = (dx*dx + dy*dy) + dz*dz in fp32 with dx = candidate - query; a candidate wins with a strict d < best from
+// best = 3.4e38, so the first minimum wins (ties, exact copies included: the smallest index, also across candidate segments).
+// Contract the backward relies on: EVERY returned index lies in [0, m) (resp. [0, n)), whatever the coordinates.  A query or
+// candidate with a nan / inf coordinate gives d = nan or +inf, which never wins: such a candidate is never returned, and such a
+// query (like any query farther than 3.4e38 from everything) gets dist = 3.4e38, idx = 0.
+// b == 0 or n == m == 0: returns without touching the outputs; exactly one empty cloud is refused.
 extern "C" int l4d_chamfer_fwd(const float* xyz1, const float* xyz2, int32_t b, int32_t n, int32_t m, float* dist1, float* dist2,
                                int32_t* idx1, int32_t* idx2, void* workspace, void* stream_) {
   if (b == 0 || (n == 0 && m == 0)) return 0;

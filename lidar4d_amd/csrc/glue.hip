@@ -343,13 +343,15 @@ extern "C" int l4d_flow_loss_finish(const float* partial, int32_t n_partial, con
 
 // dy16[k][0..5] = fp16(dy[k][0..5] * g * s), columns 6..15 zero, with s = 2^k the power of two that puts amax * |g| * s into
 // [2^11, 2^12) (flow_field.py: fp16 adjoints normalised per call ON THE DEVICE; k clamped to +-40); inv_out[0] = 1 / s.  A
-// non-finite g or amax gives non-finite dy16: the overflow reaches the parameter gradients and the scaler (common.h f2h_grad).
+// non-finite g or amax gives non-finite dy16 in EVERY one of the six columns of every row: the overflow reaches the parameter
+// gradients and the scaler (common.h f2h_grad).  g does that through the product; amax = +inf (l4d_flow_loss_finish: some dy is
+// inf / nan) or nan would otherwise only pick a clamped k and leave the finite rows finite, so it is tested for.
 __global__ void __launch_bounds__(256) flow_dy16_kernel(const float* __restrict__ dy, int n, const float* __restrict__ g,
                                                         const float* __restrict__ amax, half_t* __restrict__ dy16, float* __restrict__ inv_out) {
   const float gg = g[0];
   const float a = fmaxf(amax[0] * fabsf(gg), 1e-30f);
   const float kf = fminf(fmaxf(floorf(log2f(4096.0f / a)), -40.0f), 40.0f);
-  const float s = exp2f(kf) * gg;  // (power of two) x upstream gradient
+  const float s = nonfinite(amax[0]) ? __builtin_nanf("") : exp2f(kf) * gg;  // (power of two) x upstream gradient
   const int k = blockIdx.x * blockDim.x + threadIdx.x;
   if (k == 0) inv_out[0] = exp2f(-kf);
   if (k >= n) return;

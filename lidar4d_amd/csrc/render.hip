@@ -432,8 +432,14 @@ __global__ void __launch_bounds__(256) attr_scatter_bwd_kernel(const int32_t* __
   half_t vr[16], vi[16];
 #pragma unroll
   for (int e = 0; e < 16; ++e) { vr[e] = (half_t)0.0f; vi[e] = (half_t)0.0f; }
-  vr[0] = f2h_grad(d_attr[p * 2 + 0] * sr * (1.0f - sr) * loss_scale);
-  vi[0] = f2h_grad(d_attr[p * 2 + 1] * si * (1.0f - si) * loss_scale);
+  // The fp32 product is rounded BEFORE the fp16 conversion (torch: fp32 tensor, then .half()).  Written as one expression the
+  // compiler folds the last multiply into the conversion (v_fma_mixlo_f16 x, loss_scale, +0: one rounding instead of two, which
+  // -ffp-contract=off does not cover, and a product of -0 comes out as +0); the empty asm keeps the two steps apart.
+  float gr = d_attr[p * 2 + 0] * sr * (1.0f - sr) * loss_scale;
+  float gi = d_attr[p * 2 + 1] * si * (1.0f - si) * loss_scale;
+  asm volatile("" : "+v"(gr), "+v"(gi));
+  vr[0] = f2h_grad(gr);
+  vi[0] = f2h_grad(gi);
   uint4* dr = reinterpret_cast<uint4*>(dy_raydrop + j * 16);
   uint4* di = reinterpret_cast<uint4*>(dy_intensity + j * 16);
   dr[0] = reinterpret_cast<uint4*>(vr)[0]; dr[1] = reinterpret_cast<uint4*>(vr)[1];
@@ -607,6 +613,10 @@ extern "C" int l4d_attr_scatter_bwd(const int32_t* idx, const int32_t* count, in
   return 0;
 }
 
+// Two kernels, two contracts for the columns of dh the gather does not feed (pinned by tests/test_gpu_glue_ops.py): with 16 aligned
+// columns at n_enc (n_enc % 8 == 0, n_enc + 16 <= in_pad) the row kernel stores the WHOLE row of every listed sample, column 0 and
+// columns above n_geo as +0 (the density gradient is written into column 0 afterwards); otherwise the generic kernel stores columns
+// 1 .. n_geo only and leaves the rest of the row as it was.  Rows of samples not listed are never touched.
 extern "C" int l4d_attr_gather_bwd(const int32_t* idx, const int32_t* count, int64_t cap, const void* dxa_raydrop,
                                    const void* dxa_intensity, int32_t in_pad, int32_t n_enc, int32_t n_geo, void* dh,
                                    int32_t h_layout, void* stream) {
