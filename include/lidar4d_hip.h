@@ -29,7 +29,7 @@ extern "C" {
 #endif
 
 #define L4D_MAX_LEVELS 16
-#define L4D_ABI_VERSION 3
+#define L4D_ABI_VERSION 4
 
 /* Multi-resolution hash grid geometry (tiny-cuda-nn "HashGrid" encoding).
  * Filled by host code (lidar4d_amd/gridmeta.py) exactly as tiny-cuda-nn's host code derives it. */
@@ -334,22 +334,11 @@ int l4d_chamfer_bwd(const float* xyz1, const float* xyz2, int32_t b, int32_t n, 
                     const float* grad_dist2, const int32_t* idx1, const int32_t* idx2, float* grad_xyz1,
                     float* grad_xyz2, void* stream);
 
-/* ---- step glue: batch assembly and loss evaluation either side of the render path, one launch each (csrc/glue.hip) ----
- * l4d_lidar_ray_batch: rows / cols [n] int64 = the drawn pixels (data/base_dataset.py:36-70; cols are taken modulo W);
- * pose [4,4] row-major sensor-to-world; (fov_up, fov) in degrees; image [H,W,3] ground-truth range image or null.
- * -> rays_o, rays_d [n,3] (base_dataset.py:72-102), gt [n,3] = image at the pixels (kitti360_dataset.py:181-187),
- * inds [n] = row * W + col. */
-int l4d_lidar_ray_batch(const int64_t* rows, const int64_t* cols, int32_t n, const float* pose, float fov_up, float fov,
-                        int32_t H, int32_t W, const float* image, float* rays_o, float* rays_d, float* gt, int64_t* inds,
-                        void* stream);
-/* model/runner.py:179-213 with the default criteria: loss[0] = sum over rays of alpha_d |d - d_gt| m + alpha_r (r - clamp(m,
- * smooth, 1 - smooth))^2 + alpha_i ((i - i_gt) m)^2 with m = gt[:,0]; g_depth [n], g_image [n,2] = its gradients;
- * pts (or null) [2,n,3] = predicted / ground-truth points along the rays in metres (runner.py:215-218: rays_d * depth * m / scale). */
-int64_t l4d_glue_workspace(int32_t n); /* floats of scratch (`partial`) the two calls below need for n rays */
-int l4d_lidar_losses(const float* depth, const float* image, const float* gt, const float* rays_d, int32_t n, float alpha_d,
-                     float alpha_r, float alpha_i, float smooth, float scale, float* loss, float* g_depth, float* g_image,
-                     float* pts, float* partial, void* stream);
-/* ray-chamfer term (runner.py:215-220) behind l4d_chamfer_fwd on pts: loss[0] += coef * sum(dist1 + dist2) and g_depth +=
+/* ---- step glue: loss evaluation behind the render path, one launch each (csrc/glue.hip).  The ray batch and the three primary
+ * losses are l4ds_ray_batch / l4ds_primary_losses (lidar4d_step.h). ---- */
+int64_t l4d_glue_workspace(int32_t n); /* floats of scratch (`partial`) l4d_ray_chamfer_grad needs for n rays */
+/* ray-chamfer term (runner.py:215-220) behind l4d_chamfer_fwd on pts [2,n,3] = predicted / ground-truth points along the rays in
+ * metres (runner.py:215-218: rays_d * depth * m / scale, m = gt[:,0]): loss[0] += coef * sum(dist1 + dist2) and g_depth +=
  * its gradient wrt the rendered depth (coef = 0.5 / n / world for the reference's mean * 0.5). */
 int l4d_ray_chamfer_grad(const float* pts, const float* rays_d, const float* gt, const float* dist1, const float* dist2,
                          const int32_t* idx1, const int32_t* idx2, int32_t n, float coef, float scale, float* loss,

@@ -3,10 +3,10 @@
  *
  * The reference preloads a sequence's ground truth as fp16 (data/kitti360_dataset.py:141-147), draws a step's rays as pixels or
  * px x py pixel patches of one frame (data/base_dataset.py:36-102) and evaluates the three primary losses with any of four
- * criteria each (main_lidar4d.py:63-66, model/runner.py:179-213).  liblidar4d_hip.so (include/lidar4d_hip.h) has the fp32 /
- * single-pixel / default-criteria forms of both (l4d_lidar_ray_batch, l4d_lidar_losses), which stay what they are; this library
- * has the general forms.  A library of its own, next to liblidar4d_prep.so, liblidar4d_eval.so, liblidar4d_loss.so and
- * liblidar4d_patch.so: loaded on first use, and the other libraries' ABIs stay what they are.
+ * criteria each (main_lidar4d.py:63-66, model/runner.py:179-213).  These two entry points are the only ray batch and the only
+ * primary losses the project has: every dataset and every criterion set goes through them, the benchmarked fp32 / single-pixel /
+ * l1-mse-mse step included.  A library of its own, next to liblidar4d_prep.so, liblidar4d_eval.so, liblidar4d_loss.so and
+ * liblidar4d_patch.so: loaded on first use.
  *
  * Conventions as in lidar4d_loss.h: every pointer is a DEVICE pointer; tensors are dense; `stream` is a hipStream_t passed as
  * void*, last; outputs and workspaces are allocated by the caller and may arrive uninitialised; every entry point returns 0
@@ -14,9 +14,9 @@
  * synchronises with the host, none calls memset, none uses floating-point atomics: the same input gives the same bits.
  *
  * fp32 discipline: the element-wise arithmetic is written in the reference's operation order and compiled without
- * contraction.  Ray origins and directions are those of l4d_lidar_ray_batch, operation for operation; for L4DS_L1 depth,
- * L4DS_MSE ray-drop and L4DS_MSE intensity on fp32 ground truth l4ds_primary_losses gives the bits of l4d_lidar_losses (same
- * workgroup size, same two-stage sum).
+ * contraction, and the loss is summed in a fixed order (csrc/glue_dev.h), so that a numpy float32 evaluation in the same order
+ * gives the bits of l4ds_primary_losses for L4DS_L1 depth, L4DS_MSE ray-drop and L4DS_MSE intensity on fp32 ground truth
+ * (tests/realdata_cases.py primary_losses_ref).
  */
 #ifndef LIDAR4D_STEP_H
 #define LIDAR4D_STEP_H

@@ -12,7 +12,7 @@ LIB_PATH = os.environ.get("L4D_LIB", os.path.join(_HERE, "liblidar4d_hip.so"))  
 L4D_MAX_LEVELS = 16
 L4D_MAX_TIME_SLICES = 8
 L4D_MAX_PLANE_SCALES = 8
-ABI_VERSION = 3
+ABI_VERSION = 4
 
 
 class GridDesc(C.Structure):
@@ -103,9 +103,7 @@ SIGNATURES = {
     "l4d_chamfer_workspace": [I32, I32, I32],
     "l4d_chamfer_fwd": [P, P, I32, I32, I32, P, P, P, P, P, P],
     "l4d_chamfer_bwd": [P, P, I32, I32, I32, P, P, P, P, P, P, P],
-    "l4d_lidar_ray_batch": [P, P, I32, P, F32, F32, I32, I32, P, P, P, P, P, P],
     "l4d_glue_workspace": [I32],
-    "l4d_lidar_losses": [P, P, P, P, I32, F32, F32, F32, F32, F32, P, P, P, P, P, P],
     "l4d_ray_chamfer_grad": [P, P, P, P, P, P, P, I32, F32, F32, P, P, P, P],
     "l4d_scale_buffers": [P, P, I64, P, P, I64, P, P],
     "l4d_flow_xt": [P, I32, P, F32, P, P],

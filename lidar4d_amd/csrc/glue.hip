@@ -5,13 +5,10 @@
 // ~5 us per step (1.3 ms of kernel time + the gaps between them, profiles/r03_kernel_stats_final.txt) -- a third of the
 // reference's own 1,024-ray step.  A captured graph does not shrink them (the step is GPU-bound); fusing does.
 //
-//   l4d_lidar_ray_batch     drawn pixels -> rays_o / rays_d / ground-truth pixels            (base_dataset.py:72-102 + the gather
-//                                                                                              of kitti360_dataset.py:181-187)
-//   l4d_lidar_losses        the three primary losses, their gradients, and the two point sets of the ray-chamfer term
-//                           (runner.py:179-219)
 //   l4d_ray_chamfer_grad    mean of the chamfer distances + their gradient wrt the rendered depth (runner.py:215-220 under autograd)
 //   l4d_scale_buffers       g *= s[0] for the saved gradients (s = the upstream gradient, i.e. the loss scale, on the device)
 //
+// The two ends of the step -- the ray batch and the three primary losses -- are csrc/stepglue.hip's (liblidar4d_step.so).
 // All arithmetic is written in the reference's operation order (this file is compiled without fma contraction), so that the
 // results agree with the torch path to the last bit wherever torch itself is deterministic (everything but its reductions).
 #include <algorithm>
@@ -19,47 +16,6 @@
 #include "common.h"
 #include "glue_dev.h"
 
-// ---- ray batch -------------------------------------------------------------------------------------------------------------
-__global__ void __launch_bounds__(256) lidar_ray_batch_kernel(const int64_t* __restrict__ rows, const int64_t* __restrict__ cols, int n,
-                                                              const float* __restrict__ pose, float fov_up, float fov, int H, int W,
-                                                              const float* __restrict__ image, float* __restrict__ rays_o,
-                                                              float* __restrict__ rays_d, float* __restrict__ gt,
-                                                              int64_t* __restrict__ inds) {
-  const int k = blockIdx.x * blockDim.x + threadIdx.x;
-  if (k >= n) return;
-  const int64_t r = rows[k], c = cols[k] % W;
-  const int64_t ind = r * W + c;
-  inds[k] = ind;
-  // base_dataset.py:82-93: i = column, j = row (floats); beta = -(i - W/2) / W * 2 * pi; alpha = (fov_up - j / H * fov) / 180 * pi
-  const float i = (float)c, j = (float)r;
-  const float pi = 3.14159265358979323846f;
-  const float beta = -(i - (float)((double)W / 2.0)) / (float)W * 2.0f * pi;
-  const float alpha = (fov_up - j / (float)H * fov) / 180.0f * pi;
-  const float ca = cosf(alpha), sa = sinf(alpha), cb = cosf(beta), sb = sinf(beta);
-  const float d[3] = {ca * cb, ca * sb, sa};
-#pragma unroll
-  for (int a = 0; a < 3; ++a) {  // rays_d = directions @ R^T, rays_o = translation
-    rays_d[k * 3 + a] = d[0] * pose[a * 4 + 0] + d[1] * pose[a * 4 + 1] + d[2] * pose[a * 4 + 2];
-    rays_o[k * 3 + a] = pose[a * 4 + 3];
-  }
-  if (image) {
-#pragma unroll
-    for (int a = 0; a < 3; ++a) gt[k * 3 + a] = image[ind * 3 + a];
-  }
-}
-
-extern "C" int l4d_lidar_ray_batch(const int64_t* rows, const int64_t* cols, int32_t n, const float* pose, float fov_up, float fov,
-                                   int32_t H, int32_t W, const float* image, float* rays_o, float* rays_d, float* gt, int64_t* inds,
-                                   void* stream) {
-  if (n <= 0) return 0;
-  if (H <= 0 || W <= 0) { l4d_set_error(1, "l4d_lidar_ray_batch: empty image"); return 1; }
-  L4D_LAUNCH(lidar_ray_batch_kernel, dim3((n + 255) / 256), dim3(256), 0, (hipStream_t)stream, rows, cols, n, pose, fov_up, fov, H, W,
-             image, rays_o, rays_d, gt, inds);
-  L4D_LAUNCH_CHECK("l4d_lidar_ray_batch");
-  return 0;
-}
-
-// ---- primary losses --------------------------------------------------------------------------------------------------------
 // fixed-order sum of one value per thread over the workgroup (1024 threads): the same result every run
 __device__ __forceinline__ float block_sum_1024(float v, float* red /* [1024] */) {
   red[threadIdx.x] = v;
@@ -74,55 +30,9 @@ __device__ __forceinline__ float block_sum_1024(float v, float* red /* [1024] */
   return r;
 }
 
-// runner.py:179-213 with the default criteria (L1 depth, MSE ray-drop on the label-smoothed mask, MSE intensity), all masked by
-// the ground-truth ray-drop and summed (partial[block] = the block's share); pts: [2][n][3] predicted / ground-truth points along
-// the rays in metres (runner.py:215-218)
-__global__ void __launch_bounds__(256) lidar_losses_kernel(const float* __restrict__ depth, const float* __restrict__ image,
-                                                          const float* __restrict__ gt, const float* __restrict__ rays_d, int n,
-                                                          float alpha_d, float alpha_r, float alpha_i, float smooth, float scale,
-                                                          float* __restrict__ partial, float* __restrict__ g_depth,
-                                                          float* __restrict__ g_image, float* __restrict__ pts) {
-  __shared__ float red[256];
-  float acc = 0.0f;
-  const int k = blockIdx.x * 256 + threadIdx.x;
-  if (k < n) {
-    const float m = gt[k * 3 + 0];
-    const float gt_i = gt[k * 3 + 1] * m, gt_d = gt[k * 3 + 2] * m;
-    const float p_r = image[k * 2 + 0], p_i = image[k * 2 + 1] * m, p_d = depth[k] * m;
-    const float gs = fminf(fmaxf(m, smooth), 1.0f - smooth);
-    const float ed = p_d - gt_d, er = p_r - gs, ei = p_i - gt_i;
-    acc = alpha_d * fabsf(ed) + alpha_r * (er * er) + alpha_i * (ei * ei);
-    g_depth[k] = alpha_d * (ed > 0.0f ? 1.0f : ed < 0.0f ? -1.0f : 0.0f) * m;
-    g_image[k * 2 + 0] = alpha_r * (2.0f * er);
-    g_image[k * 2 + 1] = alpha_i * (2.0f * ei) * m;
-    if (pts) {
-#pragma unroll
-      for (int a = 0; a < 3; ++a) {
-        const float rd = rays_d[k * 3 + a];
-        pts[k * 3 + a] = rd * p_d / scale;
-        pts[(n + k) * 3 + a] = rd * gt_d / scale;
-      }
-    }
-  }
-  const float total = block_sum_256(acc, red);
-  if (threadIdx.x == 0) partial[blockIdx.x] = total;
-}
-
-// partial: scratch of l4d_glue_workspace(n) floats
+// ---- ray-chamfer term ------------------------------------------------------------------------------------------------------
+// partial of l4d_ray_chamfer_grad: scratch of l4d_glue_workspace(n) floats
 extern "C" int64_t l4d_glue_workspace(int32_t n) { return (int64_t)(n > 0 ? (n + 255) / 256 : 1); }
-
-extern "C" int l4d_lidar_losses(const float* depth, const float* image, const float* gt, const float* rays_d, int32_t n, float alpha_d,
-                                float alpha_r, float alpha_i, float smooth, float scale, float* loss, float* g_depth, float* g_image,
-                                float* pts, float* partial, void* stream) {
-  if (n < 0) { l4d_set_error(1, "l4d_lidar_losses: negative ray count"); return 1; }
-  const int blocks = (n + 255) / 256;
-  if (blocks > 0)
-    L4D_LAUNCH(lidar_losses_kernel, dim3(blocks), dim3(256), 0, (hipStream_t)stream, depth, image, gt, rays_d, n, alpha_d, alpha_r, alpha_i,
-               smooth, scale, partial, g_depth, g_image, pts);
-  L4D_LAUNCH(sum_partials_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, (const float*)partial, blocks, 1.0f, 0, loss);
-  L4D_LAUNCH_CHECK("l4d_lidar_losses");
-  return 0;
-}
 
 // loss[0] += coef * sum(dist1 + dist2); g_depth += coef * d(sum)/d(depth) through p_k = rays_d_k * (depth_k * m_k) / scale:
 //   dist1_k = |p_k - q_idx1[k]|^2  -> 2 (p_k - q_a) . rays_d_k * m_k / scale

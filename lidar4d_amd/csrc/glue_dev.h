@@ -1,6 +1,7 @@
 // What csrc/glue.hip (liblidar4d_hip.so) and csrc/stepglue.hip (liblidar4d_step.so) share: the fixed-order sum of a 256-thread
-// workgroup and the one-workgroup sum of the per-workgroup partials.  One definition, so that the two libraries' primary-loss entry
-// points reduce in the same order and give the same bits.
+// workgroup and the one-workgroup sum of the per-workgroup partials.  One definition, so that the primary losses
+// (l4ds_primary_losses) and the ray-chamfer term added to them (l4d_ray_chamfer_grad) reduce in one fixed order, the one
+// tests/realdata_cases.py fixed_order_sum restates.
 #pragma once
 #include "common.h"
 

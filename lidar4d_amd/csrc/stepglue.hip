@@ -1,5 +1,5 @@
-// The two ends of a training step on a real sequence (include/lidar4d_step.h, liblidar4d_step.so): the general forms of
-// csrc/glue.hip's l4d_lidar_ray_batch and l4d_lidar_losses, ONE sweep over the rays each.
+// The two ends of a training step (include/lidar4d_step.h, liblidar4d_step.so): the ray batch and the primary losses of every
+// dataset and criterion set, ONE sweep over the rays each.
 //
 //   l4ds_ray_batch        drawn patch corners -> pixel indices, rays_o / rays_d, and the drawn pixels' ground truth in the frame's own
 //                         type (the reference preloads fp16: data/kitti360_dataset.py:141-147); the px x py patch is expanded
@@ -7,9 +7,10 @@
 //   l4ds_primary_losses   runner.py:179-213 for any of the four criteria per term and fp32 or fp16 ground truth: value,
 //                         gradients, optionally the ray-chamfer term's point sets and an fp32 copy of the ground truth
 //
-// Both stream over n rays, a thread per ray, 12 to 60 bytes each way: nothing to stage, the only LDS is the workgroup sum.  The
-// arithmetic of the origins / directions and of the L1 / MSE / MSE case is csrc/glue.hip's, operation for operation (this file is
-// compiled without fma contraction too), and the sum is the same two stages (glue_dev.h): those cases give the same bits.
+// Both stream over n rays, a thread per ray, 12 to 60 bytes each way: nothing to stage, the only LDS is the workgroup sum.  All
+// arithmetic is written in the reference's operation order (this file is compiled without fma contraction) and the loss is summed
+// in two fixed-order stages (glue_dev.h): the same input gives the same bits, and the L1 / MSE / MSE case on fp32 ground truth
+// those of a numpy float32 evaluation in the same order (tests/realdata_cases.py primary_losses_ref).
 #include <stdio.h>
 
 #include "common.h"
@@ -42,7 +43,7 @@ __global__ void __launch_bounds__(256) step_ray_batch_kernel(const int64_t* __re
   if (c < 0) c += W;
   const int64_t ind = r * W + c;
   inds[k] = ind;
-  // base_dataset.py:82-93, as lidar_ray_batch_kernel (csrc/glue.hip) evaluates it
+  // base_dataset.py:82-93: i = column, j = row (floats); beta = -(i - W/2) / W * 2 * pi; alpha = (fov_up - j / H * fov) / 180 * pi
   const float i = (float)c, j = (float)r;
   const float pi = 3.14159265358979323846f;
   const float beta = -(i - (float)((double)W / 2.0)) / (float)W * 2.0f * pi;
@@ -86,8 +87,7 @@ extern "C" int l4ds_ray_batch(const int64_t* top, const int64_t* left, int32_t n
 }
 
 // ---- primary losses --------------------------------------------------------------------------------------------------------
-// One criterion at prediction a and target b: the value, and dv = d value / d a as autograd gives it.  L1 and MSE are the
-// expressions of lidar_losses_kernel (csrc/glue.hip).
+// One criterion at prediction a and target b: the value, and dv = d value / d a as autograd gives it.
 __device__ __forceinline__ float step_criterion(int kind, float a, float b, float delta, float& dv) {
   const float e = a - b;
   switch (kind) {

@@ -24,6 +24,13 @@ def pixel_block_order(rows, cols):
     return torch.argsort(key)
 
 
+def _patch_shape(patch_size):
+    """(px, py) of the reference's ``patch_size_lidar``: an int, [p] or [px, py]."""
+    if isinstance(patch_size, int):
+        return patch_size, patch_size
+    return (int(patch_size[0]), int(patch_size[0])) if len(patch_size) == 1 else (int(patch_size[0]), int(patch_size[1]))
+
+
 def get_lidar_rays(poses, intrinsics, H, W, N=-1, patch_size=1, generator=None, sort_pixels=False):
     """poses [B,4,4] sensor-to-world, intrinsics (fov_up, fov) in degrees -> dict(rays_o, rays_d [B,n,3], inds [B,n]).
     N > 0 draws pixels the way the reference does (base_dataset.py:36-70): ``N // (px * py)`` patches of px x py pixels
@@ -35,12 +42,7 @@ def get_lidar_rays(poses, intrinsics, H, W, N=-1, patch_size=1, generator=None, 
     B = poses.shape[0]
     if N > 0:
         N = min(N, H * W)
-        if isinstance(patch_size, int):
-            px, py = patch_size, patch_size
-        elif len(patch_size) == 1:
-            px, py = patch_size[0], patch_size[0]
-        else:
-            px, py = patch_size
+        px, py = _patch_shape(patch_size)
         if px > 0:
             n_patch = N // (px * py)
             top = torch.randint(0, H - px, size=[n_patch], device=device, generator=generator)
@@ -71,6 +73,22 @@ def get_lidar_rays(poses, intrinsics, H, W, N=-1, patch_size=1, generator=None, 
     return {"rays_o": rays_o, "rays_d": rays_d, "inds": inds}
 
 
+def draw_ray_batch(who, gen, num_rays, patch_size, pose, fov, H, W, image):
+    """A training step's batch of one frame on a HIP device: the two ``randint``s of get_lidar_rays from ``gen`` (same bounds,
+    sizes and order, so the same generator consumption), then ONE launch for patch expansion, pixel index, direction, rotation,
+    origin and the ground-truth gather (ops.ray_batch_patches; 33 torch launches otherwise) -> rays_o, rays_d [1,n,3], the
+    drawn pixels of ``image`` [H,W,3] in its own dtype [1,n,3].  ``who`` names the caller in the error message."""
+    from . import ops
+    px, py = _patch_shape(patch_size)
+    n = min(num_rays, H * W)
+    n_patch = n // (px * py)
+    if n_patch * px * py != n:
+        raise ValueError(f"{who}: num_rays = {n} is not a multiple of the patch size {px} x {py}")
+    top = torch.randint(0, H - px, size=[n_patch], device=gen.device, generator=gen)
+    left = torch.randint(0, W, size=[n_patch], device=gen.device, generator=gen)
+    return ops.ray_batch_patches(top, left, (px, py), pose, fov, H, W, image)[:3]
+
+
 def _analytic_scene_depth(origin, dirs):
     """Metric range along unit ``dirs`` [n,3] from ``origin`` [3] to a ground plane z = -1.7 and five boxes."""
     inf = torch.full(dirs.shape[:1], float("inf"), device=dirs.device)
@@ -99,7 +117,7 @@ class SyntheticKitti360:
                  sort_pixels=False, frame_seed=None):
         self.device, self.H, self.W, self.num_frames, self.num_rays = device, H, W, num_frames, num_rays
         self.patch_size_lidar = 1  # settable like the reference's dataset attribute (runner.py:700-705): int or [px, py]
-        self.fused_batch = True  # batch_for: one HIP launch behind the two random draws (False: the torch restatement)
+        self.fused_batch = True  # batch_for: draw_ray_batch, one HIP launch behind the two random draws (False: the torch restatement)
         self.sort_pixels = sort_pixels  # pixel_block_order; measured SLOWER on MI355X (66.3 vs 63.5 ms/step: neighbouring rays
         # pile onto the same LDS histogram bins / cache lines), kept as an option for experiments
         self.scale, self.fov = scale, fov
@@ -158,24 +176,10 @@ class SyntheticKitti360:
         pose = self.poses[frame:frame + 1]
         t = self.times[frame]
         # (num_rays <= 0 = "every pixel of the frame" in get_lidar_rays, kitti360_dataset.py:150-180: that case takes the torch path)
-        patch = self.patch_size_lidar
-        px, py = (patch, patch) if isinstance(patch, int) else ((patch[0], patch[0]) if len(patch) == 1 else tuple(patch))
+        px = _patch_shape(self.patch_size_lidar)[0]
         if self.fused_batch and self.num_rays > 0 and torch.device(self.device).type == "cuda" and px > 0 and not self.sort_pixels:
-            # the two draws of get_lidar_rays (same generator consumption), then ONE launch for pixel index, direction,
-            # rotation, origin and the ground-truth gather (csrc/glue.hip: 33 torch launches otherwise)
-            from . import ops
-            n = min(self.num_rays, self.H * self.W)
-            n_patch = n // (px * py)
-            if n_patch * px * py != n:
-                raise ValueError(f"SyntheticKitti360.batch_for: num_rays = {n} is not a multiple of the patch size {px} x {py}")
-            top = torch.randint(0, self.H - px, size=[n_patch], device=self.device, generator=self.gen)
-            left = torch.randint(0, self.W, size=[n_patch], device=self.device, generator=self.gen)
-            if px * py > 1:  # a patch's pixels: rows top + 0 .. px - 1, columns left + 0 .. py - 1 around the panorama, patch-row major
-                dr = torch.arange(px, device=self.device).repeat_interleave(py)
-                dc = torch.arange(py, device=self.device).repeat(px)
-                top = (top[:, None] + dr[None, :]).reshape(-1)
-                left = ((left[:, None] + dc[None, :]) % self.W).reshape(-1)
-            rays_o, rays_d, images, _ = ops.lidar_ray_batch(top, left, self.poses[frame], self.fov, self.H, self.W, self.images[frame])
+            rays_o, rays_d, images = draw_ray_batch("SyntheticKitti360.batch_for", self.gen, self.num_rays, self.patch_size_lidar,
+                                                    self.poses[frame], self.fov, self.H, self.W, self.images[frame])
             return {"rays_o_lidar": rays_o, "rays_d_lidar": rays_d, "time": t, "images_lidar": images,
                     "poses_lidar": pose, "H_lidar": self.H, "W_lidar": self.W, "index": [frame],
                     "time_host": frame / (self.num_frames - 1)}

@@ -22,7 +22,7 @@ import numpy as np
 import torch
 from torch.utils.data import DataLoader, RandomSampler
 
-from .data import get_lidar_rays
+from .data import _patch_shape, draw_ray_batch, get_lidar_rays
 
 # first and last frame id of the sequences the reference knows (kitti360_dataset.py:29-71)
 SEQUENCE_FRAMES = {
@@ -138,7 +138,7 @@ class KITTI360Dataset:
     @property
     def device_batches(self):
         """``batch_for`` draws on the device and copies nothing from the host (what a captured step needs): preloaded there."""
-        px = self.patch_size_lidar if isinstance(self.patch_size_lidar, int) else self.patch_size_lidar[0]
+        px = _patch_shape(self.patch_size_lidar)[0]
         return bool(self.preload) and torch.device(self.device).type == "cuda" and self.num_rays_lidar > 0 and px > 0
 
     def batch_for(self, k):
@@ -148,17 +148,8 @@ class KITTI360Dataset:
         H, W = self.H_lidar, self.W_lidar
         extra = {"index": [k], "time_host": self.times_host[k]}
         if self.device_batches:
-            from . import ops
-            from .trainer import _patch_shape
-            px, py = _patch_shape(self.patch_size_lidar)
-            n = min(self.num_rays_lidar, H * W)
-            n_patch = n // (px * py)
-            if n_patch * px * py != n:
-                raise ValueError(f"KITTI360Dataset.batch_for: num_rays_lidar = {n} is not a multiple of the patch size {px} x {py}")
-            top = torch.randint(0, H - px, size=[n_patch], device=self.device, generator=self.gen)
-            left = torch.randint(0, W, size=[n_patch], device=self.device, generator=self.gen)
-            rays_o, rays_d, images, _ = ops.ray_batch_patches(top, left, (px, py), self.poses_lidar[k], self.intrinsics_lidar, H, W,
-                                                              self.images_lidar[k])
+            rays_o, rays_d, images = draw_ray_batch("KITTI360Dataset.batch_for", self.gen, self.num_rays_lidar, self.patch_size_lidar,
+                                                    self.poses_lidar[k], self.intrinsics_lidar, H, W, self.images_lidar[k])
             return {"H_lidar": H, "W_lidar": W, "rays_o_lidar": rays_o, "rays_d_lidar": rays_d, "images_lidar": images,
                     "time": self._times_dev[k], "poses_lidar": self.poses_lidar[k:k + 1], **extra}
         poses = self.poses_lidar[[k]].to(self.device)

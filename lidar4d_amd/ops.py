@@ -566,41 +566,7 @@ def dyn_pairs_build(slice_tables16, pairs):
     call("l4d_dyn_pairs_build", _ptrs(slice_tables16), len(slice_tables16), n_entries, _p(pairs), _stream())
 
 
-# ---- step glue (csrc/glue.hip): batch assembly and loss evaluation, one launch each ------------------------------------------
-def lidar_ray_batch(rows, cols, pose, fov, H, W, image=None):
-    """Drawn pixels (rows / cols [n] int64 on the device) of one frame -> rays_o, rays_d [1,n,3], gt [1,n,3] (None without
-    ``image`` [H,W,3]), inds [1,n]: data/base_dataset.py:72-102 and the gather of kitti360_dataset.py:181-187 in one launch."""
-    _chk(rows, torch.int64, "rows"), _chk(cols, torch.int64, "cols"), _chk(pose, torch.float32, "pose")
-    n, dev = rows.numel(), rows.device
-    pose = pose.reshape(4, 4).contiguous()
-    rays_o = torch.empty(1, n, 3, dtype=torch.float32, device=dev)
-    rays_d = torch.empty(1, n, 3, dtype=torch.float32, device=dev)
-    inds = torch.empty(1, n, dtype=torch.int64, device=dev)
-    gt = None
-    if image is not None:
-        _chk(image, torch.float32, "image")
-        image = image.contiguous()
-        gt = torch.empty(1, n, 3, dtype=torch.float32, device=dev)
-    call("l4d_lidar_ray_batch", _p(rows.contiguous()), _p(cols.contiguous()), n, _p(pose), float(fov[0]), float(fov[1]), int(H), int(W),
-         _p(image), _p(rays_o), _p(rays_d), _p(gt), _p(inds), _stream())
-    return rays_o, rays_d, gt, inds
-
-
-def lidar_losses(depth, image, gt, rays_d, alpha_d, alpha_r, alpha_i, smooth, scale, want_points):
-    """runner.py:179-213 (default criteria) -> loss [1], g_depth [n], g_image [n,2], pts [2,n,3] or None."""
-    for t, nm in ((depth, "depth"), (image, "image"), (gt, "gt"), (rays_d, "rays_d")):
-        _chk(t, torch.float32, nm)
-    n, dev = depth.numel(), depth.device
-    loss = torch.empty(1, dtype=torch.float32, device=dev)
-    g_depth = torch.empty(n, dtype=torch.float32, device=dev)
-    g_image = torch.empty(n, 2, dtype=torch.float32, device=dev)
-    pts = torch.empty(2, n, 3, dtype=torch.float32, device=dev) if want_points else None
-    partial = torch.empty((n + 255) // 256 + 1, dtype=torch.float32, device=dev)
-    call("l4d_lidar_losses", _p(depth), _p(image), _p(gt), _p(rays_d), n, float(alpha_d), float(alpha_r), float(alpha_i), float(smooth),
-         float(scale), _p(loss), _p(g_depth), _p(g_image), _p(pts), _p(partial), _stream())
-    return loss, g_depth, g_image, pts
-
-
+# ---- step glue (csrc/stepglue.hip, csrc/glue.hip): batch assembly and loss evaluation, one launch each ------------------------
 def ray_batch_patches(top, left, patch, pose, fov, H, W, image=None):
     """l4ds_ray_batch (include/lidar4d_step.h): drawn patch corners (top / left [n_patch] int64 on the device) and the patch shape
     ``patch`` = (px, py) -> rays_o, rays_d [1,n,3], gt [1,n,3] in ``image``'s dtype, fp32 or fp16 (None without ``image`` [H,W,3]),

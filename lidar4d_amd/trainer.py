@@ -16,6 +16,7 @@ import torch
 import torch.distributed as dist
 
 from . import ops
+from .data import _patch_shape
 from .params import bump_epoch
 
 
@@ -58,35 +59,26 @@ def lidar_loss(outputs, images_lidar, alpha_d=1.0, alpha_r=0.01, alpha_i=0.1, sm
     return loss.sum()
 
 
-DEFAULT_CRITERIA = ("l1", "mse", "mse")  # depth, ray-drop, intensity (main_lidar4d.py:63-66)
-
-
 class _PrimaryLossFn(torch.autograd.Function):
-    """``lidar_loss`` (+ ``ray_chamfer_loss / world``) as one autograd node: forward = l4d_lidar_losses (csrc/glue.hip) for the
-    reference's default criteria on fp32 ground truth, l4ds_primary_losses (csrc/stepglue.hip, liblidar4d_step.so) for fp16
-    ground truth or any other criterion (+ l4d_chamfer_fwd, l4d_ray_chamfer_grad), which also leaves the gradients wrt the
-    rendered depth / image; backward = one launch that scales them by the upstream gradient (the loss scale, a device scalar).
-    Replaces ~70 element-wise torch launches per step (runner.py:179-220 as torch evaluates it)."""
+    """``lidar_loss`` (+ ``ray_chamfer_loss / world``) as one autograd node: forward = l4ds_primary_losses (csrc/stepglue.hip,
+    liblidar4d_step.so) for any criterion per term and fp32 or fp16 ground truth (+ l4d_chamfer_fwd, l4d_ray_chamfer_grad), which
+    also leaves the gradients wrt the rendered depth / image; backward = one launch that scales them by the upstream gradient
+    (the loss scale, a device scalar).  Replaces ~70 element-wise torch launches per step (runner.py:179-220 as torch evaluates
+    it)."""
 
     @staticmethod
     def forward(ctx, depth, image, gt, rays_d, alpha_d, alpha_r, alpha_i, smooth, scale, chamfer, world, kinds):
         c = lambda t, *shape: t.detach().to(torch.float32).reshape(*shape).contiguous()
         n = depth.numel()
         rd_c = c(rays_d, n, 3)
-        if gt.dtype == torch.float16 or tuple(kinds) != DEFAULT_CRITERIA:
-            gt_c = gt.detach().reshape(n, 3)
-            gt_c = (gt_c if gt_c.dtype == torch.float16 else gt_c.to(torch.float32)).contiguous()
-            want32 = bool(chamfer) and gt_c.dtype == torch.float16  # (ops.ray_chamfer_accumulate reads the mask as fp32)
-            loss, g_depth, g_image, pts, gt32 = ops.primary_losses_any(c(depth, n), c(image, n, 2), gt_c, rd_c, kinds, alpha_d, alpha_r,
-                                                                       alpha_i, smooth, 0.2 * scale, scale, want_points=bool(chamfer),
-                                                                       want_gt32=want32)
-            gt_c = gt32 if want32 else gt_c
-        else:
-            gt_c = c(gt, n, 3)
-            loss, g_depth, g_image, pts = ops.lidar_losses(c(depth, n), c(image, n, 2), gt_c, rd_c, alpha_d, alpha_r, alpha_i, smooth,
-                                                           scale, want_points=bool(chamfer))
+        gt_c = gt.detach().reshape(n, 3)
+        gt_c = (gt_c if gt_c.dtype == torch.float16 else gt_c.to(torch.float32)).contiguous()
+        want32 = bool(chamfer) and gt_c.dtype == torch.float16  # (ops.ray_chamfer_accumulate reads the mask as fp32)
+        loss, g_depth, g_image, pts, gt32 = ops.primary_losses_any(c(depth, n), c(image, n, 2), gt_c, rd_c, kinds, alpha_d, alpha_r,
+                                                                   alpha_i, smooth, 0.2 * scale, scale, want_points=bool(chamfer),
+                                                                   want_gt32=want32)
         if chamfer:
-            ops.ray_chamfer_accumulate(pts, rd_c, gt_c, 0.5 / max(n, 1) / world, scale, loss, g_depth)
+            ops.ray_chamfer_accumulate(pts, rd_c, gt32 if want32 else gt_c, 0.5 / max(n, 1) / world, scale, loss, g_depth)
         ctx.save_for_backward(g_depth, g_image)
         ctx.shapes = (depth.shape, image.shape)
         return loss.reshape(())
@@ -219,8 +211,7 @@ def depth_grad_loss(pred_depth, gt_depth, gt_raydrop, patch_size, scale, alpha_g
     is smooth (|gradient| < 0.01) and has a return -- the reference only uses the x direction there, which is kept --
     summed and weighted by alpha_grad; the optional smoothness terms are means over the patch gradients.
     pred_depth / gt_depth / gt_raydrop: [1, n] in ray order (patch-major), depths already masked by the ray-drop."""
-    px, py = (patch_size, patch_size) if isinstance(patch_size, int) else \
-        ((patch_size[0], patch_size[0]) if len(patch_size) == 1 else tuple(patch_size))
+    px, py = _patch_shape(patch_size)
     loss = pred_depth.new_zeros(())
     if px <= 1:
         return loss
@@ -256,13 +247,6 @@ def depth_grad_loss(pred_depth, gt_depth, gt_raydrop, patch_size, scale, alpha_g
             raise ValueError(f"depth_grad_loss: unknown kind {kind!r}")
         loss = loss + alpha_grad * term.sum()
     return loss
-
-
-def _patch_shape(patch_size):
-    """(px, py) of the reference's ``patch_size_lidar``: an int, [p] or [px, py]."""
-    if isinstance(patch_size, int):
-        return patch_size, patch_size
-    return (int(patch_size[0]), int(patch_size[0])) if len(patch_size) == 1 else (int(patch_size[0]), int(patch_size[1]))
 
 
 class _PatchGradLossFn(torch.autograd.Function):

@@ -20,8 +20,6 @@ int main(void) {
       (fn_t)&l4d_attr_scatter_bwd,
       (fn_t)&l4d_cast_f32_to_f16,
       (fn_t)&l4d_chamfer_bwd,
-      (fn_t)&l4d_lidar_ray_batch,
-      (fn_t)&l4d_lidar_losses,
       (fn_t)&l4d_glue_workspace,
       (fn_t)&l4d_ray_chamfer_grad,
       (fn_t)&l4d_scale_buffers,

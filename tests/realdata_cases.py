@@ -52,6 +52,74 @@ def fixture_dataset(root, split, device="cpu", fp16=True, num_rays=64, H=8, W=32
                            offset=cfg["offset"], fp16=fp16, num_rays_lidar=num_rays, fov_lidar=cfg["fov_lidar"], **kw)
 
 
+def loss_inputs(n, half, seed=0, device="cpu"):
+    """-> depth [n], image [n,2], gt [n,3] (fp16 if ``half``), rays_d [n,3], scene scale: n rays with dropped ones, exact hits, and
+    depth / intensity errors on both sides of Huber's delta (0.2 * scale)."""
+    from lidar4d_amd.data import KITTI360_SCALE as S
+    g = torch.Generator(device=device).manual_seed(seed)
+    u = lambda *s: torch.rand(*s, device=device, generator=g)
+    gt = torch.stack([(u(n) > 0.25).float(), u(n), (4.0 + 60.0 * u(n)) * S], -1)
+    gt = gt.half() if half else gt
+    wide = (u(n) > 0.5).float()  # half of the errors well inside delta, half well beyond it
+    depth = (gt[:, 2].float() + (u(n) - 0.5) * S * (0.2 + 3.8 * wide)).clamp_min(0.0)
+    inten = gt[:, 1].float() + (u(n) - 0.5) * (0.2 * S + 0.5 * wide)
+    depth[: n // 8] = gt[: n // 8, 2].float()
+    image = torch.stack([u(n) * 1.4 - 0.2, inten], -1)
+    rays_d = torch.nn.functional.normalize(u(n, 3) - 0.5, dim=-1)
+    return depth.contiguous(), image.contiguous(), gt.contiguous(), rays_d.contiguous(), S
+
+
+F32 = np.float32
+PRIMARY_REF_N = (1, 255, 256, 257, 1000, 65793)  # 65,793 rays = 258 partials: the second stage's strided loop takes a second turn
+PRIMARY_REF_SETTINGS = ((0.2, (1.0, 0.01, 0.1)), (0.1, (0.7, 0.05, 0.2)))  # (smooth, (alpha_d, alpha_r, alpha_i))
+
+
+def _tree_256(red):
+    """csrc/glue_dev.h block_sum_256 on every row of ``red`` [rows, 256] fp32: red[t] += red[t + s] for s = 128 ... 1."""
+    red = red.copy()
+    s = 128
+    while s:
+        red[:, :s] = red[:, :s] + red[:, s:2 * s]
+        s >>= 1
+    return red[:, 0]
+
+
+def fixed_order_sum(values):
+    """E (tests/glue_cases.py): the sum of one fp32 value per ray as the loss kernels take it (csrc/glue_dev.h).  Per workgroup of
+    256 rays block_sum_256, rays past the end counting +0; then sum_partials_kernel: thread t adds partial[t], partial[t + 256],
+    ... to +0 in index order, the same tree over the 256 threads, and loss = 0 + 1 * total."""
+    v = np.asarray(values)
+    assert v.dtype == F32 and v.ndim == 1
+    pad = lambda a: np.concatenate([a, np.zeros(-a.size % 256, F32)]).reshape(-1, 256)
+    acc = np.zeros(256, F32)
+    for turn in pad(_tree_256(pad(v))):  # (a missing partial[t + 256 j] adds nothing in the kernel; + 0 here changes no bit: acc is never -0)
+        acc = acc + turn
+    return F32(0.0) + F32(1.0) * _tree_256(acc[None])[0]
+
+
+def primary_losses_ref(depth, image, gt, rays_d, alpha_d, alpha_r, alpha_i, smooth, scale):
+    """E (tests/glue_cases.py: numpy float32, scalars rounded to fp32 first, no contraction, IEEE division): what
+    l4ds_primary_losses gives for L4DS_L1 depth, L4DS_MSE ray-drop, L4DS_MSE intensity on fp32 ground truth, every expression in the
+    order step_primary_losses_kernel (csrc/stepglue.hip) writes it -> dict(loss [1], g_depth [n], g_image [n,2], pts [2,n,3],
+    gt32 [n,3]).  Nothing here is computed by HIP code."""
+    depth, image, gt, rays_d = (np.ascontiguousarray(a, dtype=F32) for a in (depth, image, gt, rays_d))
+    alpha_d, alpha_r, alpha_i, smooth, scale = (F32(a) for a in (alpha_d, alpha_r, alpha_i, smooth, scale))
+    m = gt[:, 0]
+    gt_i, gt_d = gt[:, 1] * m, gt[:, 2] * m
+    gs = np.minimum(np.maximum(m, smooth), F32(1.0) - smooth)
+    p_r, p_i, p_d = image[:, 0], image[:, 1] * m, depth * m
+    e_d, e_r, e_i = p_d - gt_d, p_r - gs, p_i - gt_i
+    v_d, dv_d = np.abs(e_d), (e_d > 0).astype(F32) - (e_d < 0).astype(F32)  # L4DS_L1: |e|, and 1 / -1 / +0
+    v_r, dv_r = e_r * e_r, F32(2.0) * e_r                # L4DS_MSE
+    v_i, dv_i = e_i * e_i, F32(2.0) * e_i
+    acc = alpha_d * v_d + alpha_r * v_r + alpha_i * v_i  # (left to right, each product rounded first)
+    g_image = np.stack([alpha_r * dv_r, alpha_i * dv_i * m], -1)
+    pts = np.stack([rays_d * p_d[:, None] / scale, rays_d * gt_d[:, None] / scale])
+    out = dict(loss=np.array([fixed_order_sum(acc)]), g_depth=alpha_d * dv_d * m, g_image=g_image, pts=pts, gt32=gt.copy())
+    assert all(a.dtype == F32 for a in out.values())
+    return out
+
+
 def evaluate_fused(c, device):
     """-> (loss, leaves) of case ``c`` with every term that has a fused node on that node (primary losses + ray chamfer, line of
     sight, patch terms); the scene-flow term replays the fixture's flow leaves through the torch restatement, as

@@ -1,4 +1,4 @@
-"""The fused step glue (csrc/glue.hip: batch assembly, primary losses + ray chamfer, scene-flow loss) against the torch
+"""The fused step glue (csrc/stepglue.hip: batch assembly, primary losses; csrc/glue.hip: ray chamfer, scene-flow loss) against the torch
 restatements of the reference's formulas they replace (``-m gpu``, MI355X).  The restatements themselves are what
 tests/test_next_rows.py / test_oracle_golden.py pin against the reference (get_lidar_rays goldens, flow loss vs oracle)."""
 import numpy as np
@@ -35,7 +35,7 @@ def test_fused_ray_batch_equals_get_lidar_rays():
 
 @pytest.mark.parametrize("chamfer,world", [(False, 1), (True, 1), (True, 4)])
 def test_fused_primary_losses_equal_torch_losses(chamfer, world):
-    """trainer.primary_losses (l4d_lidar_losses [+ l4d_chamfer_fwd + l4d_ray_chamfer_grad], backward = l4d_scale_buffers) ==
+    """trainer.primary_losses (l4ds_primary_losses [+ l4d_chamfer_fwd + l4d_ray_chamfer_grad], backward = l4d_scale_buffers) ==
     lidar_loss [+ ray_chamfer_loss / world] (runner.py:179-220) in value and in the gradients wrt the rendered depth / image,
     under an upstream gradient (the loss scale) that is not 1."""
     from lidar4d_amd.data import KITTI360_SCALE, SyntheticKitti360
@@ -191,7 +191,7 @@ def test_training_losses_vs_reference_train_step_on_device(tag):
 
 
 def test_fused_primary_losses_vs_reference_train_step():
-    """The fused primary-loss node (l4d_lidar_losses + l4d_chamfer_fwd + l4d_ray_chamfer_grad: what the benchmarked step runs)
+    """The fused primary-loss node (l4ds_primary_losses + l4d_chamfer_fwd + l4d_ray_chamfer_grad: what the benchmarked step runs)
     against the reference's train_step on the default criteria: loss value, d loss / d depth, d loss / d image."""
     from lidar4d_amd.trainer import primary_losses
     from tests import train_golden

@@ -139,10 +139,11 @@ def test_same_input_same_bits(name, kw):
 
 
 # ---- 5. the patch batch on the fused draw -----------------------------------------------------------------------------------------
-@pytest.mark.parametrize("patch", [[2, 8], 3])
-def test_patch_batch_fused_vs_torch(patch):
+@pytest.mark.parametrize("patch,rays", [([2, 8], 144), (3, 144), ([2, 8], 256)], ids=["patch0", "3", "patch0-256"])
+def test_patch_batch_fused_vs_torch(patch, rays):
+    """SyntheticKitti360.batch_for on a patch batch: the draw with the patches expanded in the kernel (data.draw_ray_batch) against
+    the same dataset's torch route for the same seed.  144 rays: 9 patches of 2 x 8, 16 of 3 x 3; 256: a full workgroup of 2 x 8."""
     from lidar4d_amd.data import SyntheticKitti360
-    rays = 144  # 9 patches of 2 x 8, 16 of 3 x 3
     out = {}
     for fused in (True, False):
         data = SyntheticKitti360(DEV, H=16, W=64, num_frames=3, num_rays=rays, seed=11)

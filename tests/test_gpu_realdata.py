@@ -1,5 +1,5 @@
 """Training on a preprocessed sequence, on the device (``-m gpu``, MI355X): the sixth library's two entry points
-(include/lidar4d_step.h) against the torch route and against the render library's fp32 / default-criteria forms, the fused
+(include/lidar4d_step.h) against the torch route and against an exact numpy emulation of the default criteria, the fused
 primary-loss node on both train-step fixtures, and ``Trainer`` on ``KITTI360Dataset`` with fp16 ground truth -- eager, captured,
 and as the reference's whole ``train()``."""
 import itertools
@@ -33,8 +33,7 @@ def test_ray_batch_equals_torch_route(tmp_path, fp16):
     """ops.ray_batch_patches against the torch route for the same corners: single pixels at n = 1, 255, 256, 257 (one workgroup
     short of, at, and past its 256 threads) and 2 x 8 patches whose left corners sit in the last columns (the wrap at W): the same
     ``inds``, bit-equal ground truth IN THE FRAME'S DTYPE, bit-equal origins, directions within 2e-7 (the bound of
-    test_fused_ray_batch_equals_get_lidar_rays: the torch path rotates with a batched GEMM); twice the same bits; and, on an fp32
-    frame, single pixels bit for bit what l4d_lidar_ray_batch gives."""
+    test_fused_ray_batch_equals_get_lidar_rays: the torch path rotates with a batched GEMM); twice the same bits."""
     from lidar4d_amd import ops
     ds = rc.fixture_dataset(tmp_path, "train", device=DEV, fp16=fp16)
     H, W, dt = ds.H_lidar, ds.W_lidar, torch.float16 if fp16 else torch.float32
@@ -58,9 +57,6 @@ def test_ray_batch_equals_torch_route(tmp_path, fp16):
         assert all(torch.equal(a, b) for a, b in zip((rays_o, rays_d, gt, inds), again))
         no_gt = ops.ray_batch_patches(*args[:-1])
         assert no_gt[2] is None and torch.equal(no_gt[1], rays_d)
-        if px == py == 1 and not fp16:
-            old = ops.lidar_ray_batch(top, left, ds.poses_lidar[k], ds.intrinsics_lidar, H, W, ds.images_lidar[k])
-            assert all(torch.equal(a, b) for a, b in zip((rays_o, rays_d, gt, inds), old))
 
 
 @pytest.mark.parametrize("fp16", [True, False])
@@ -96,35 +92,29 @@ def test_fused_losses_vs_reference_train_step(which, tag):
 
 
 def _loss_inputs(n, half, seed=0):
-    """n rays with dropped ones, exact hits, and depth / intensity errors on both sides of Huber's delta (0.2 * scale)."""
-    from lidar4d_amd.data import KITTI360_SCALE as S
-    g = torch.Generator(device=DEV).manual_seed(seed)
-    u = lambda *s: torch.rand(*s, device=DEV, generator=g)
-    gt = torch.stack([(u(n) > 0.25).float(), u(n), (4.0 + 60.0 * u(n)) * S], -1)
-    gt = gt.half() if half else gt
-    wide = (u(n) > 0.5).float()  # half of the errors well inside delta, half well beyond it
-    depth = (gt[:, 2].float() + (u(n) - 0.5) * S * (0.2 + 3.8 * wide)).clamp_min(0.0)
-    inten = gt[:, 1].float() + (u(n) - 0.5) * (0.2 * S + 0.5 * wide)
-    depth[: n // 8] = gt[: n // 8, 2].float()
-    image = torch.stack([u(n) * 1.4 - 0.2, inten], -1)
-    rays_d = torch.nn.functional.normalize(u(n, 3) - 0.5, dim=-1)
-    return depth.contiguous(), image.contiguous(), gt.contiguous(), rays_d.contiguous(), S
+    return rc.loss_inputs(n, half, seed, DEV)
 
 
-@pytest.mark.parametrize("n", [1, 255, 256, 257, 1000])
+@pytest.mark.parametrize("n", rc.PRIMARY_REF_N)
 def test_default_criteria_on_fp32_equal_lidar_losses_bit_for_bit(n):
-    """l1 / mse / mse on fp32 ground truth: l4ds_primary_losses gives the bits of l4d_lidar_losses in loss, both gradients and
-    both point sets (same workgroup size, same two-stage sum) -- what lets a later change retire the old entry point."""
+    """l1 / mse / mse on fp32 ground truth: l4ds_primary_losses gives the bits of rc.primary_losses_ref, the numpy float32
+    evaluation in the kernel's order that no HIP code computes (tests/test_realdata_cpu.py pins it against float64): loss through
+    the fixed-order sum of csrc/glue_dev.h, both gradients, both point sets and the fp32 copy of the ground truth.  n on both
+    sides of a workgroup, and 65,793 rays = 258 partials, where the second stage's strided loop takes a second turn."""
     from lidar4d_amd import ops
     depth, image, gt, rays_d, S = _loss_inputs(n, half=False, seed=n)
-    for smooth, alphas in ((0.2, (1.0, 0.01, 0.1)), (0.1, (0.7, 0.05, 0.2))):
+    host = [t.cpu().numpy() for t in (depth, image, gt, rays_d)]
+    for smooth, alphas in rc.PRIMARY_REF_SETTINGS:
+        want = {k: torch.from_numpy(v) for k, v in rc.primary_losses_ref(*host, *alphas, smooth, S).items()}
         for points in (True, False):
-            old = ops.lidar_losses(depth, image, gt, rays_d, *alphas, smooth, S, want_points=points)
             new = ops.primary_losses_any(depth, image, gt, rays_d, ("l1", "mse", "mse"), *alphas, smooth, 0.2 * S, S, want_points=points,
                                          want_gt32=True)
-            assert float(old[0]) != 0.0 and torch.equal(new[4], gt)
-            for a, b in zip(old, new[:4]):
-                assert (a is None and b is None) or torch.equal(a, b)
+            got = dict(zip(("loss", "g_depth", "g_image", "pts", "gt32"), new))
+            assert float(got["loss"]) != 0.0
+            if not points:
+                assert got.pop("pts") is None
+            for name, t in got.items():
+                assert torch.equal(t.cpu(), want[name]), (name, points, smooth)
 
 
 @pytest.mark.parametrize("half", [True, False])

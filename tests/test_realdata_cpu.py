@@ -109,6 +109,66 @@ def test_criterion_takes_half_targets_as_autocast_does():
         assert torch.equal(v, w) and torch.equal(a.grad, a32.grad)
 
 
+@pytest.mark.parametrize("n", rc.PRIMARY_REF_N)
+def test_primary_losses_ref_vs_lidar_loss_in_float64(n, monkeypatch):
+    """rc.primary_losses_ref -- what tests/test_gpu_realdata.py holds l4ds_primary_losses to, bit for bit -- against
+    ``trainer.lidar_loss`` and its autograd in float64 on the same inputs and the same fp32-rounded scalars (``criterion``'s casts
+    to float, the autocast policy, are taken out for the float64 evaluation; the expressions stay).  Per-ray outputs: within
+    2 fp32 ulps of the float64 value -- each is at most three roundings of 2^-24 relative behind exact operands (a difference of two
+    fp32 values, a square or a doubling, a weight; a product and a quotient for the points).  Loss: within
+    (3 n + 2) * 2^-24 * sum |terms|, the bound of glue_cases.flow_loss_finish_ref: 3 n - 1 additions in any order, and up to
+    three roundings inside a term.  One constant differs between the two evaluations: the kernel takes the upper smoothing target
+    1 - smooth in fp32; its rounding error d enters the ray-drop gradient of the rays with a return as 2 alpha_r d and their terms
+    as alpha_r (2 |e_r| + d) d, which the two bounds are widened by (d < 2^-25: below 2e-9 on a gradient of 1e-2)."""
+    from lidar4d_amd import trainer as T
+    F32, F64 = np.float32, np.float64
+    plain = {"l1": lambda a, b: (a - b).abs(), "mse": lambda a, b: (a - b) ** 2}
+    monkeypatch.setattr(T, "criterion", lambda kind, scale=1.0: plain[kind])
+    depth, image, gt, rays_d, S = rc.loss_inputs(n, half=False, seed=n)
+    host = [t.numpy() for t in (depth, image, gt, rays_d)]
+    ulps = lambda got, want64: np.abs(got.astype(F64) - want64) / np.spacing(np.abs(want64).astype(F32)).astype(F64)
+    for smooth, alphas in rc.PRIMARY_REF_SETTINGS:
+        ref = rc.primary_losses_ref(*host, *alphas, smooth, S)
+        a_d, a_r, a_i, s32, S32 = (float(F32(v)) for v in (*alphas, smooth, S))
+        d64, i64 = depth.double()[None].requires_grad_(True), image.double()[None].requires_grad_(True)
+        loss = T.lidar_loss({"depth_lidar": d64, "image_lidar": i64}, gt.double()[None], a_d, a_r, a_i, s32, scale=S32)
+        loss.backward()
+        loss = loss.detach()
+        m = gt[:, 0].double()
+        d_hi = abs(float(F32(1.0) - F32(smooth)) - (1.0 - s32))
+        assert d_hi < 2.0 ** -25 and set(m.tolist()) <= {0.0, 1.0}
+        e_r = (image[:, 0].double() - (1.0 - s32)).abs() * m
+        bound = (3 * n + 2) * 2.0 ** -24 * float(loss) + a_r * float(((2 * e_r + d_hi) * d_hi * m).sum())
+        assert float(loss) > 0 and abs(float(ref["loss"][0]) - float(loss)) <= bound, (n, smooth, float(ref["loss"][0]), float(loss), bound)
+        pts64 = torch.stack([rays_d.double() * (depth.double() * m)[:, None] / S32, rays_d.double() * (gt[:, 2].double() * m)[:, None] / S32])
+        slack = np.zeros((n, 2))
+        slack[:, 0] = 2 * a_r * d_hi * m.numpy()
+        for name, want, extra in (("g_depth", d64.grad[0], 0.0), ("g_image", i64.grad[0], slack), ("pts", pts64, 0.0)):
+            want = want.numpy()
+            off = np.abs(ref[name].astype(F64) - want) - extra
+            worst = float((off / np.spacing(np.abs(want).astype(F32)).astype(F64)).max())
+            assert ref[name].shape == want.shape and worst <= 2.0, (name, n, smooth, worst)
+            assert n < 255 or float(np.abs(want).max()) > 0
+        assert np.array_equal(ref["gt32"], host[2])
+
+
+def test_fixed_order_sum_drops_and_doubles_no_term():
+    """rc.fixed_order_sum on its own: exact on integers (as any order is), also where the second stage takes a second turn, and
+    on real values within the bound of its longest chain of additions."""
+    F32 = np.float32
+    r = np.random.RandomState(5)
+    ints = r.randint(-8, 9, size=65793).astype(F32)
+    assert float(rc.fixed_order_sum(ints)) == float(ints.astype(np.float64).sum())
+    assert float(rc.fixed_order_sum(np.zeros(0, F32))) == 0.0 and float(rc.fixed_order_sum(np.array([2.5], F32))) == 2.5
+    # thread t of the second stage adds partial[t] and partial[t + 256]: 258 workgroups of one 1.0 each, the last two landing on threads 0 and 1
+    v = np.zeros(258 * 256, F32)
+    v[::256] = 1.0
+    assert float(rc.fixed_order_sum(v)) == 258.0
+    x = r.uniform(0.0, 1.0, size=65793).astype(F32)
+    exact = float(x.astype(np.float64).sum())
+    assert abs(float(rc.fixed_order_sum(x)) - exact) <= 19 * 2.0 ** -24 * exact  # (positive terms, 8 + 2 + 8 additions deep)
+
+
 @pytest.mark.parametrize("which,tag", rc.ALL_CASES)
 def test_lidar_loss_vs_reference_train_step(which, tag, monkeypatch):
     """The torch restatement of the whole loss block against the reference's train_step, at tests/train_golden.py's CPU bound

@@ -6,8 +6,7 @@ model and dataset, frame 25) with an fp16 copy of the ground truth, at 1,024 and
                commit does for any criterion set but l1 / mse / mse (the scene-flow term stays on its fused node on both sides)
 
 for a non-default criterion set (huber / bce / l1) and for the default set; and the default fp32 step (SyntheticKitti360 as it
-is, l4d_lidar_ray_batch + l4d_lidar_losses), which this change must leave alone.  Writes profiles/realdata_step_times.txt to the
-path given (default: stdout).
+is: the same two entry points on fp32 ground truth).  Writes profiles/realdata_step_times.txt to the path given (default: stdout).
 
 Method (that of tools/patch_grad_times.py): a host clock around STEPS eager steps that end in a device synchronise, after the loss
 scale has settled; median / min / max of ROUNDS rounds, the configurations alternating.  Launches: the device kernels torch's
@@ -31,24 +30,9 @@ OTHER = dict(depth_loss="huber", raydrop_loss="bce", intensity_loss="l1")
 
 
 def make_dataset(n_rays, half, fused):
-    from lidar4d_amd import ops
     from lidar4d_amd.data import SyntheticKitti360
-
-    class HalfGroundTruth(SyntheticKitti360):
-        """SyntheticKitti360 with its frames held in half, as KITTI360Dataset preloads them; the device draw is KITTI360Dataset's."""
-
-        def batch_for(self, frame):
-            if not self.fused_batch:
-                return super().batch_for(frame)
-            top = torch.randint(0, self.H - 1, size=[self.num_rays], device=self.device, generator=self.gen)
-            left = torch.randint(0, self.W, size=[self.num_rays], device=self.device, generator=self.gen)
-            rays_o, rays_d, images, _ = ops.ray_batch_patches(top, left, (1, 1), self.poses[frame], self.fov, self.H, self.W, self.images[frame])
-            return {"rays_o_lidar": rays_o, "rays_d_lidar": rays_d, "time": self.times[frame], "images_lidar": images,
-                    "poses_lidar": self.poses[frame:frame + 1], "H_lidar": self.H, "W_lidar": self.W, "index": [frame],
-                    "time_host": frame / (self.num_frames - 1)}
-
-    data = (HalfGroundTruth if half else SyntheticKitti360)("cuda", W=1024, num_rays=n_rays, seed=1000, frame_seed=1000)
-    if half:
+    data = SyntheticKitti360("cuda", W=1024, num_rays=n_rays, seed=1000, frame_seed=1000)
+    if half:  # the frames held in half, as KITTI360Dataset preloads them (the device draw is the one both datasets share)
         data.images = data.images.half()
     data.fused_batch = fused
     return data
