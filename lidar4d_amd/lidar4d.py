@@ -3,7 +3,8 @@
 ``get_params``) and state-dict keys, on HIP kernels.
 
 * ``render`` / ``run`` -> the fused pipeline of lidar4d_amd/fused.py (what the reference's Trainer and
-  Simulator call: runner.py:183,398,447; simulator.py:115).
+  Simulator call: runner.py:183,398,447; simulator.py:115).  With 4 or 16 channels per hex-plane (``fused`` is False) ``run`` is
+  ``LiDAR_Renderer.run`` over ``density`` / ``attribute`` below, same result keys.
 * ``density`` / ``attribute`` / ``flow`` -> operator-level modules, for callers that use them directly
   (runner.py:227,252 calls ``flow``).
 
@@ -13,6 +14,7 @@ MIOpen; it is not part of the flat parameter arenas (the reference trains it sep
 import numpy as np
 import torch
 
+from . import ops
 from . import tcnn
 from .activation import trunc_exp
 from .flow_field import FlowField
@@ -22,6 +24,25 @@ from .params import ParamStore
 from .planes_field import Planes4D
 from .renderer import LiDAR_Renderer
 from .unet import UNet
+
+
+class _MarkTimeSlicesFn(torch.autograd.Function):
+    """Identity on the density.  Its backward makes every ``.grad`` a view of the flat gradient arena (so that what autograd
+    accumulates from here on lands there) and raises the arena's gates for the time-slice pair of this call's frame."""
+
+    @staticmethod
+    def forward(ctx, sigma, model, tinfo):
+        ctx.model = model
+        ctx.save_for_backward(tinfo)
+        return sigma.view_as(sigma)
+
+    @staticmethod
+    def backward(ctx, d_sigma):
+        (tinfo,) = ctx.saved_tensors
+        store = ctx.model._store
+        store.prepare_grads()
+        ops.mark_time_slices(tinfo, ctx.model.hash_encoder.hash_dynamic[0].time_resolution, store.gates)
+        return d_sigma, None, None
 
 
 class LiDAR4D(LiDAR_Renderer):
@@ -59,6 +80,16 @@ class LiDAR4D(LiDAR_Renderer):
                 or any(hd.num_basis != 4 for hd in he.hash_dynamic)):
             raise ValueError("LiDAR4D: the fused pipeline needs n_features_per_level_hash = 4 (num_basis 4), reduction = 'concat' and "
                              "decompose = True for its hash encoder; other HashGrid4D options are available at operator level only")
+        # The fused pipeline is also built for eight channels per plane.  Four and sixteen (Planes4D's other widths) render and train
+        # through LiDAR_Renderer.run over density() / attribute(), the plane half of density() as one launch each way
+        # (Planes4D.density_features, liblidar4d_planes.so): slower, gradients through autograd.
+        self.fused = n_features_per_level_plane == 8
+        n_sigma_in = self.planes_encoder.n_output_dims + self.hash_encoder.n_output_dims
+        sigma_pad = (n_sigma_in + 15) // 16 * 16
+        if not self.fused and sigma_pad not in tcnn.IN_PADS:
+            raise ValueError(f"LiDAR4D: n_features_per_level_plane = {n_features_per_level_plane} with {n_levels_plane} plane scales and "
+                             f"{n_levels_hash} hash levels gives the density network {n_sigma_in} input columns, padded to {sigma_pad}; "
+                             f"the MLP kernels have the padded widths {', '.join(map(str, tcnn.IN_PADS))}")
         self.view_encoder = tcnn.Encoding(n_input_dims=3, encoding_config={"otype": "Frequency", "degree": 12})
         self.flow_net = FlowField(input_dim=4, num_layers=num_layers_flow, hidden_dim=hidden_dim_flow, use_grid=True)
 
@@ -104,6 +135,8 @@ class LiDAR4D(LiDAR_Renderer):
         (parity tests feed the oracle's noise).  ``time_host``: the value of ``time`` as a python float when the caller
         has it (the training loop does): spares the one device read-back of a training step -- the host-side copy of
         hash_field.py:79-85's slice choice below, which would otherwise wait for the whole previous step to drain."""
+        if not self.fused:  # four or sixteen channels per plane: sampling, density(), compositing, attribute() one after the other
+            return LiDAR_Renderer.run(self, rays_o, rays_d, time, num_steps=num_steps, perturb=perturb, noise=noise)
         prefix = rays_o.shape[:-1]
         rays_o = rays_o.contiguous().view(-1, 3).float()
         rays_d = rays_d.contiguous().view(-1, 3).float()
@@ -152,8 +185,13 @@ class LiDAR4D(LiDAR_Renderer):
         frame_idx = int(np.float32(float(t)) * np.float32(self.num_frames - 1))
         hash_feat_s, hash_feat_d = self.hash_encoder(x, t)
         xt = torch.cat([x, t.expand(x.shape[0], 1)], dim=-1)
-        plane_feat_s, plane_feat_d = self.planes_encoder(xt)
         flow = self.flow_net(xt).float()
+        tinfo = None
+        if self.fused:
+            plane_feat_s, plane_feat_d = self.planes_encoder(xt)
+        else:  # the plane half -- static product, the three time products, the blend -- as one node (l4dh_density_planes_fwd / _bwd)
+            tinfo = ops.time_setup(t.reshape(1), self.num_frames)
+            plane_feat_s, plane_feat_d = self.planes_encoder.density_features(xt, flow, tinfo)
         hash_feat_1 = hash_feat_2 = hash_feat_d
         plane_feat_1 = plane_feat_2 = plane_feat_d
         if frame_idx < self.num_frames - 1:
@@ -161,18 +199,26 @@ class LiDAR4D(LiDAR_Renderer):
             t1 = torch.tensor((frame_idx + 1) / self.num_frames)
             with torch.no_grad():
                 hash_feat_1 = self.hash_encoder.forward_dynamic(x1, t1)
-            plane_feat_1 = self.planes_encoder.forward_dynamic(torch.cat([x1, t1.to(x1).expand(x1.shape[0], 1)], dim=-1))
+            if self.fused:
+                plane_feat_1 = self.planes_encoder.forward_dynamic(torch.cat([x1, t1.to(x1).expand(x1.shape[0], 1)], dim=-1))
         if frame_idx > 0:
             x2 = x + flow[:, 3:]
             t2 = torch.tensor((frame_idx - 1) / self.num_frames)
             with torch.no_grad():
                 hash_feat_2 = self.hash_encoder.forward_dynamic(x2, t2)
-            plane_feat_2 = self.planes_encoder.forward_dynamic(torch.cat([x2, t2.to(x2).expand(x2.shape[0], 1)], dim=-1))
-        plane_feat_d = 0.5 * plane_feat_d + 0.25 * (plane_feat_1 + plane_feat_2)
+            if self.fused:
+                plane_feat_2 = self.planes_encoder.forward_dynamic(torch.cat([x2, t2.to(x2).expand(x2.shape[0], 1)], dim=-1))
+        if self.fused:
+            plane_feat_d = 0.5 * plane_feat_d + 0.25 * (plane_feat_1 + plane_feat_2)
         hash_feat_d = 0.5 * hash_feat_d + 0.25 * (hash_feat_1 + hash_feat_2)
         features = torch.cat([plane_feat_s, plane_feat_d, hash_feat_s.float(), hash_feat_d], dim=-1)
         h = self.sigma_net(features)
-        return {"sigma": trunc_exp(h[..., 0]), "geo_feat": h[..., 1:]}
+        sigma = trunc_exp(h[..., 0])
+        if tinfo is not None and not self.reference_grad_none and torch.is_grad_enabled() and h.requires_grad:
+            # under lidar4d_amd.trainer.Trainer the gradients of this path are autograd's: its backward raises the optimiser's gates
+            # for the frame's time-slice pair, which the fused node does itself (FlatAdam leaves ungated slices alone)
+            sigma = _MarkTimeSlicesFn.apply(sigma, self, tinfo)
+        return {"sigma": sigma, "geo_feat": h[..., 1:]}
 
     def attribute(self, x, d, mask=None, geo_feat=None, **kwargs):
         if mask is not None:

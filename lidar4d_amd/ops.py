@@ -157,24 +157,77 @@ def planes_relayout(layout, planes, arena, to_channel_last=True, accumulate=Fals
     call("l4d_planes_relayout", _ptrs(planes), layout.res_flat, layout.n_scales, layout.C, _p(arena), layout.off_flat, mode, _stream())
 
 
-def planes_fwd(layout, arena, xt, which=0):
+def _planes_width_call(name, *args):
+    """Channel counts other than 8: liblidar4d_planes.so (include/lidar4d_planes.h), mapped on first use."""
+    from . import _planes_lib
+    _planes_lib.call(name, *args)
+
+
+def planes_fwd(layout, arena, xt, which=0, width_lib=None):
+    """width_lib: take liblidar4d_planes.so's kernel (l4dh_planes_fwd: 4, 8 or 16 channels) instead of liblidar4d_hip.so's (8 channels);
+    default: for every channel count but 8."""
     _chk(arena, torch.float32, "arena"), _chk(xt, torch.float32, "xt")
     P = xt.shape[0]
     n_out = layout.n_scales * layout.C
     out_s = torch.empty(P, n_out, dtype=torch.float32, device=xt.device) if which != 2 else None
     out_d = torch.empty(P, n_out, dtype=torch.float32, device=xt.device) if which != 1 else None
-    call("l4d_planes_fwd", _p(arena), layout.off_flat, layout.res_flat, layout.n_scales, layout.C, _p(xt), P, which,
-         _p(out_s), _p(out_d), _stream())
+    args = (_p(arena), layout.off_flat, layout.res_flat, layout.n_scales, layout.C, _p(xt), P, which, _p(out_s), _p(out_d), _stream())
+    if layout.C != 8 if width_lib is None else width_lib:
+        _planes_width_call("l4dh_planes_fwd", *args)
+    else:
+        call("l4d_planes_fwd", *args)
     return out_s, out_d
 
 
-def planes_bwd(layout, arena, xt, which, dout_s, dout_d, grad_arena, want_dxt):
+def planes_bwd(layout, arena, xt, which, dout_s, dout_d, grad_arena, want_dxt, width_lib=None):
     _chk(arena, torch.float32, "arena"), _chk(xt, torch.float32, "xt"), _chk(grad_arena, torch.float32, "grad_arena")
     _chk(dout_s, torch.float32, "dout_s"), _chk(dout_d, torch.float32, "dout_d")
     dxt = torch.empty_like(xt) if want_dxt else None
-    call("l4d_planes_bwd", _p(arena), layout.off_flat, layout.res_flat, layout.n_scales, layout.C, _p(xt), xt.shape[0],
-         which, _p(dout_s), _p(dout_d), _p(grad_arena), _p(dxt), _stream())
+    args = (_p(arena), layout.off_flat, layout.res_flat, layout.n_scales, layout.C, _p(xt), xt.shape[0], which, _p(dout_s),
+            _p(dout_d), _p(grad_arena), _p(dxt), _stream())
+    if layout.C != 8 if width_lib is None else width_lib:
+        _planes_width_call("l4dh_planes_bwd", *args)
+    else:
+        call("l4d_planes_bwd", *args)
     return dxt
+
+
+def _flow_rows(flow, P):
+    """(row stride in elements, is fp16) of a flow tensor [P, >= 6], fp16 or fp32, whose rows are dense: read in place, never copied."""
+    if not flow.is_cuda:
+        _chk(flow, None, "flow")  # (raises: no CPU fallback)
+    if flow.dtype not in (torch.float16, torch.float32):
+        raise TypeError(f"flow: expected torch.float16 or torch.float32, got {flow.dtype}")
+    if flow.dim() != 2 or flow.shape[0] != P or flow.shape[1] < 6 or flow.stride(1) != 1 or (P > 1 and flow.stride(0) < 6):
+        raise ValueError(f"flow: expected [{P}, >= 6] with dense rows, got {tuple(flow.shape)} with strides {tuple(flow.stride())}")
+    return int(flow.stride(0)) if P > 1 else max(int(flow.stride(0)), 6), int(flow.dtype == torch.float16)
+
+
+def density_planes_fwd(layout, arena, xt, flow, tinfo):
+    """l4dh_density_planes_fwd (include/lidar4d_planes.h): the plane half of LiDAR4D.density in one launch.  xt [P,4] fp32, flow
+    [P, >= 6] fp16 or fp32 (row stride as it comes), tinfo from ``time_setup`` -> (plane_s, plane_d) fp32 [P, n_scales * C]."""
+    _chk(arena, torch.float32, "arena"), _chk(xt, torch.float32, "xt"), _chk(tinfo, torch.float32, "tinfo")
+    P = xt.shape[0]
+    stride, is_half = _flow_rows(flow, P)
+    n_out = layout.n_scales * layout.C
+    out_s = torch.empty(P, n_out, dtype=torch.float32, device=xt.device)
+    out_d = torch.empty(P, n_out, dtype=torch.float32, device=xt.device)
+    _planes_width_call("l4dh_density_planes_fwd", _p(arena), layout.off_flat, layout.res_flat, layout.n_scales, layout.C, _p(xt),
+                       _p(flow), stride, is_half, _p(tinfo), P, _p(out_s), _p(out_d), _stream())
+    return out_s, out_d
+
+
+def density_planes_bwd(layout, arena, xt, flow, tinfo, d_out_s, d_out_d, grad_arena, want_dflow=True, want_dxt=False):
+    """Adjoint of density_planes_fwd: grad_arena += plane gradients; -> (dflow [P,6] fp32 or None, dxt [P,4] fp32 or None)."""
+    _chk(arena, torch.float32, "arena"), _chk(xt, torch.float32, "xt"), _chk(tinfo, torch.float32, "tinfo")
+    _chk(d_out_s, torch.float32, "d_out_s"), _chk(d_out_d, torch.float32, "d_out_d"), _chk(grad_arena, torch.float32, "grad_arena")
+    P = xt.shape[0]
+    stride, is_half = _flow_rows(flow, P)
+    dflow = torch.empty(P, 6, dtype=torch.float32, device=xt.device) if want_dflow else None
+    dxt = torch.empty_like(xt) if want_dxt else None
+    _planes_width_call("l4dh_density_planes_bwd", _p(arena), layout.off_flat, layout.res_flat, layout.n_scales, layout.C, _p(xt),
+                       _p(flow), stride, is_half, _p(tinfo), P, _p(d_out_s), _p(d_out_d), _p(grad_arena), _p(dflow), _p(dxt), _stream())
+    return dflow, dxt
 
 
 # ---- frequency encoding / MLP ----------------------------------------------------------------------

@@ -4,6 +4,10 @@ constructor arguments, ``planes`` ModuleList-of-ParameterList with [1, C, R_b, R
 
 One kernel samples all planes of all scales (bilinear, align_corners=True, border), takes the per-scale
 products and concatenates scales (l4d_planes_fwd / l4d_planes_bwd), instead of 24 F.grid_sample launches.
+
+Channels per plane (``output_dim``): 8, the reference's default, runs on liblidar4d_hip.so's kernels; 4 and 16 on the width-generic
+ones of liblidar4d_planes.so (l4dh_planes_fwd / l4dh_planes_bwd, include/lidar4d_planes.h), which ``density_features`` -- the plane
+half of ``LiDAR4D.density`` as one launch each way -- uses at all three widths.
 """
 import itertools
 
@@ -48,15 +52,55 @@ class _PlanesFn(torch.autograd.Function):
         return (dxt, None, None) + tuple(grads)
 
 
+class _DensityPlanesFn(torch.autograd.Function):
+    """(plane_s, plane_d) of lidar4d.py:155-176 from the sample, its flow and the call's time: l4dh_density_planes_fwd / _bwd."""
+
+    @staticmethod
+    def forward(ctx, xt, flow, tinfo, mod, *planes):
+        xt_c = xt.detach().to(torch.float32).contiguous()
+        fl = flow.detach()
+        if fl.dtype not in (torch.float16, torch.float32):
+            fl = fl.float()
+        if fl.dim() != 2 or fl.stride(1) != 1:
+            fl = fl.contiguous()
+        out_s, out_d = ops.density_planes_fwd(mod.layout, mod._arena(), xt_c, fl, tinfo)
+        ctx.mod = mod
+        ctx.save_for_backward(xt_c, fl, tinfo)
+        ctx.need_dxt, ctx.need_dflow, ctx.flow_dtype = xt.requires_grad, flow.requires_grad, flow.dtype
+        return out_s, out_d
+
+    @staticmethod
+    def backward(ctx, ds, dd):
+        xt, fl, tinfo = ctx.saved_tensors
+        mod = ctx.mod
+        n_out = mod.layout.n_scales * mod.layout.C
+        zeros = lambda: torch.zeros(xt.shape[0], n_out, dtype=torch.float32, device=xt.device)
+        ds = zeros() if ds is None else ds.float().contiguous()
+        dd = zeros() if dd is None else dd.float().contiguous()
+        garena = torch.zeros(mod.layout.numel, dtype=torch.float32, device=xt.device)
+        dflow, dxt = ops.density_planes_bwd(mod.layout, mod._arena(), xt, fl, tinfo, ds, dd, garena, want_dflow=ctx.need_dflow,
+                                            want_dxt=ctx.need_dxt)
+        grads = [torch.empty_like(p) for p in mod._flat_planes()]
+        ops.planes_relayout(mod.layout, grads, garena, to_channel_last=False)
+        if dflow is not None and (ctx.flow_dtype != torch.float32 or fl.shape[1] > 6):  # autograd wants the flow's own dtype and shape
+            full = torch.zeros(fl.shape, dtype=ctx.flow_dtype, device=fl.device)
+            full[:, :6] = dflow
+            dflow = full
+        return (dxt, dflow, None, None) + tuple(grads)
+
+
 class Planes4D(nn.Module):
+    WIDTHS = (4, 8, 16)  # channels per plane: 8 on liblidar4d_hip.so, 4 and 16 on liblidar4d_planes.so
+
     def __init__(self, grid_dimensions=2, input_dim=4, output_dim=8, resolution=(32, 32, 32, 8),
                  multiscale_res=(1, 2, 4, 8), concat_ms_feat=True, decompose=True, reduction="prod"):
         super().__init__()
         if grid_dimensions != 2 or input_dim != 4 or not concat_ms_feat or not decompose or reduction != "prod":
             raise ValueError("Planes4D: only the configuration LiDAR4D uses is implemented "
                              "(2-D planes of a 4-D input, concat over scales, decompose, reduction='prod')")
-        if output_dim != 8:
-            raise ValueError("Planes4D: the HIP kernel is specialised for 8 channels per plane")
+        if output_dim not in self.WIDTHS:
+            raise ValueError(f"Planes4D: output_dim (channels per plane) must be 4, 8 or 16, got {output_dim}: the samplers load "
+                             "four channels at a time, and the density network's input has to pad to a width the MLP kernels have")
         self.config = {"grid_dimensions": grid_dimensions, "input_dim": input_dim, "output_dim": output_dim,
                        "resolution": list(resolution)}
         self.multiscale_res = list(multiscale_res)
@@ -104,3 +148,12 @@ class Planes4D(nn.Module):
     def forward(self, input):
         s, d = _PlanesFn.apply(input, self, 0, *self._flat_planes())
         return [s, d]
+
+    def density_features(self, xt, flow, tinfo):
+        """The plane half of ``LiDAR4D.density`` (lidar4d.py:155-176) as one autograd node.  xt [P,4] = (x, y, z, t0) in [0,1];
+        flow [P, >= 6] (forward xyz, backward xyz; fp16 or fp32, read with the row stride it has); tinfo: ``ops.time_setup``'s
+        floats (t0, t1, t2, has_fwd, has_bwd).  -> (plane_s, plane_d) fp32 [P, n_output_dims / 2]: the static product at x and
+        0.5 d0 + 0.25 (d1 + d2) of the time products at (x, t0), (x + forward flow, t1), (x + backward flow, t2), a missing neighbour
+        replaced by d0.  Gradients reach the planes, ``flow`` and ``xt``."""
+        s, d = _DensityPlanesFn.apply(xt, flow, tinfo, self, *self._flat_planes())
+        return s, d

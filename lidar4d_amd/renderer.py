@@ -1,8 +1,8 @@
 """Volumetric LiDAR renderer.  Mirror of the reference's model/renderer.py:13-186 (``LiDAR_Renderer``):
 same constructor, ``run`` / ``render`` signatures, result-dict keys and shapes, staged chunking.
 
-``run`` is the fused HIP pipeline (lidar4d_amd/fused.py) when the subclass provides one (LiDAR4D does);
-otherwise it composes the subclass's ``density`` / ``attribute`` with the sampling and compositing kernels
+``run`` is the fused HIP pipeline (lidar4d_amd/fused.py) when the subclass provides one (LiDAR4D does, for eight channels per
+hex-plane); otherwise (a LiDAR4D of four or sixteen channels per plane: ``fused`` is False) it composes the subclass's ``density`` / ``attribute`` with the sampling and compositing kernels
 (l4d_sample_rays, l4d_composite_*), which is what a user-defined field subclass gets.
 """
 import os
@@ -14,26 +14,44 @@ from . import ops
 
 
 class _CompositeFn(torch.autograd.Function):
-    """weights/depth/weights_sum from sigma (renderer.py:98-126) with the analytic adjoint."""
+    """weights/depth/weights_sum from sigma (renderer.py:98-126) with the analytic adjoint; mask, and the compacted
+    `weights > 1e-4` sample indices with their number (what the fused run returns as ``mask_idx`` / ``mask_count``)."""
 
     @staticmethod
     def forward(ctx, sigma, z_vals, sample_dist, density_scale, active_sensor):
         sigma = sigma.detach().float().contiguous()
-        weights, wsum, depth, mask, _, _ = ops.composite_fwd(sigma, z_vals, sample_dist, density_scale, active_sensor,
-                                                            want_mask=True, want_idx=False)
+        weights, wsum, depth, mask, idx, count = ops.composite_fwd(sigma, z_vals, sample_dist, density_scale, active_sensor,
+                                                                  want_mask=True, want_idx=True)
         ctx.save_for_backward(sigma, z_vals, weights)
         ctx.cfg = (sample_dist, density_scale, active_sensor)
-        ctx.mark_non_differentiable(mask)
-        return weights, wsum, depth, mask
+        ctx.mark_non_differentiable(mask, idx, count)
+        return weights, wsum, depth, mask, idx, count
 
     @staticmethod
-    def backward(ctx, d_weights, d_wsum, d_depth, _):
+    def backward(ctx, d_weights, d_wsum, d_depth, _m, _i, _c):
         sigma, z_vals, weights = ctx.saved_tensors
         sample_dist, density_scale, active_sensor = ctx.cfg
         c = lambda t: None if t is None else t.float().contiguous()
         d_sigma, _ = ops.composite_bwd(sigma, z_vals, weights, None, 0, sample_dist, density_scale, active_sensor,
                                        c(d_depth), c(d_wsum), None, c(d_weights), want_d_attr=False)
         return d_sigma, None, None, None, None
+
+
+class _ImageFn(torch.autograd.Function):
+    """image = sum over a ray's samples of weights * attr (renderer.py:128) by l4d_composite_image: every ray summed in the same
+    order whatever the batch holds (a staged render is bit-identical to an unstaged one); the adjoint is elementwise."""
+
+    @staticmethod
+    def forward(ctx, weights, attr):
+        weights, attr = weights.detach().float().contiguous(), attr.detach().float().contiguous()
+        ctx.save_for_backward(weights, attr)
+        return ops.composite_image(weights, attr.view(-1, attr.shape[-1]), attr.shape[-1])
+
+    @staticmethod
+    def backward(ctx, d_image):
+        weights, attr = ctx.saved_tensors
+        d_image = d_image.float().unsqueeze(1)  # [N, 1, C]
+        return (attr * d_image).sum(-1), weights.unsqueeze(-1) * d_image
 
 
 class LiDAR_Renderer(nn.Module):
@@ -72,22 +90,26 @@ class LiDAR_Renderer(nn.Module):
         device = rays_o.device
         if perturb and noise is None:
             noise = torch.rand(N, num_steps, device=device)  # renderer.py:84
+        elif perturb:
+            noise = noise.to(device=device, dtype=torch.float32).contiguous()
         z_vals, xyzs = ops.sample_rays(rays_o, rays_d, self._lin(num_steps, device), noise if perturb else None,
                                        self.near_lidar, self.far_lidar, self.bound, want_xyz=True)
         dens = self.density(xyzs, time)
         sample_dist = (self.far_lidar - self.near_lidar) / num_steps
-        weights, wsum, depth, mask = _CompositeFn.apply(dens["sigma"].reshape(N, num_steps), z_vals, sample_dist,
-                                                        self.density_scale, self.active_sensor)
+        weights, wsum, depth, mask, idx, count = _CompositeFn.apply(dens["sigma"].reshape(N, num_steps), z_vals, sample_dist,
+                                                                    self.density_scale, self.active_sensor)
         dirs = rays_d.view(-1, 1, 3).expand(N, num_steps, 3).reshape(-1, 3)
         extra = {k: v for k, v in dens.items() if k != "sigma"}
         attr = self.attribute(xyzs, dirs, mask=mask.reshape(-1).bool(), **extra).view(N, num_steps, self.out_lidar_dim)
-        image = torch.sum(weights.unsqueeze(-1) * attr, dim=-2)
+        image = _ImageFn.apply(weights, attr)
         return {
             "depth_lidar": depth.view(*prefix),
             "image_lidar": image.view(*prefix, self.out_lidar_dim),
             "weights_sum_lidar": wsum,
             "weights": weights,
             "z_vals": z_vals,
+            "mask_idx": idx,      # as the fused run: compacted `weights > 1e-4` sample indices (renderer.py:110) ...
+            "mask_count": count,  # ... and their number (device int32)
         }
 
     # Staged inference renders a frame as 16-32 chunks of max_ray_batch rays (renderer.py:142-186).  With ``graph_staged``
@@ -128,7 +150,8 @@ class LiDAR_Renderer(nn.Module):
             out_lidar_dim = self.out_lidar_dim
             depth = torch.empty((B, N), device=device)
             image = torch.empty((B, N, out_lidar_dim), device=device)
-            graphed = (self.graph_staged and device.type == "cuda" and not torch.is_grad_enabled() and hasattr(self, "_store")
+            # (a model without the fused pipeline reads the time on the host in density(): nothing to capture)
+            graphed = (self.graph_staged and getattr(self, "fused", True) and device.type == "cuda" and not torch.is_grad_enabled() and hasattr(self, "_store")
                        and not kwargs.get("perturb", False) and kwargs.get("noise") is None and torch.is_tensor(time)
                        and time.device == device)
             for b in range(B):

@@ -89,6 +89,9 @@ def Encoding(n_input_dims, encoding_config, dtype=None, seed=1337):
     raise ValueError(f"lidar4d_amd.tcnn: unsupported encoding otype {otype!r} (LiDAR4D uses HashGrid and Frequency)")
 
 
+IN_PADS = (16, 32, 64, 96, 128, 160, 176, 192)  # padded input widths the fused MLP kernels are built for
+
+
 def mlp_layer_shapes(n_in, n_out, n_neurons, n_hidden_layers):
     in_pad = (n_in + 15) // 16 * 16
     out_pad = (n_out + 15) // 16 * 16
@@ -136,7 +139,7 @@ class FullyFusedMLP(nn.Module, _HalfParams):
         self.n_hidden_layers = int(cfg["n_hidden_layers"])
         self.shapes = mlp_layer_shapes(n_input_dims, n_output_dims, self.n_neurons, self.n_hidden_layers)
         self.in_pad = self.shapes[0][1]
-        if self.in_pad not in (16, 32, 64, 96, 128, 160, 176, 192) or not 1 <= self.n_hidden_layers <= 3:
+        if self.in_pad not in IN_PADS or not 1 <= self.n_hidden_layers <= 3:
             raise ValueError("lidar4d_amd.tcnn.Network: padded input width in {16,32,64,96,128,160,176,192} and 1..3 "
                              "hidden layers are supported")
         g = torch.Generator().manual_seed(seed)

@@ -1020,7 +1020,10 @@ class Trainer:
         process group), a dataset that draws its batch on the device (``batch_for`` + ``register`` of its generator), the
         patch terms and the line-of-sight term only as their fused nodes (``fused_patch``; ``fused_urf``: its tolerance follows
         the optimiser's schedule on the device, the torch restatement ``urf_loss`` computes it on the host from
-        ``opt.step_count``).  A ``KITTI360Dataset`` draws on the device when it is preloaded there (``device_batches``)."""
+        ``opt.step_count``).  A ``KITTI360Dataset`` draws on the device when it is preloaded there (``device_batches``).
+        A model without the fused pipeline (``model.fused`` False) is never captured."""
+        if not getattr(self.model, "fused", True):  # four or sixteen channels per plane: density() reads the time on the host
+            return False
         patches = getattr(self.dataset, "patch_size_lidar", 1) != 1 or getattr(self, "change_patch_size_lidar", None) is not None
         return (self.reducer is None and (not self.urf or getattr(self, "fused_urf", False)) and hasattr(self.dataset, "batch_for") and hasattr(self.dataset, "next_frame")
                 and getattr(self.dataset, "device_batches", True)
@@ -1117,7 +1120,7 @@ class Trainer:
         finally:
             if side is not None:
                 self.model._flow_loss_pending = None
-        if self.flow:
+        if self.flow or not getattr(self.model, "fused", True):
             st.prepare_grads()  # fold gradients autograd produced outside the fused node into the arena
         if self.reducer is not None:
             self.reducer.finish()
