@@ -47,7 +47,7 @@ import numpy as np
 from glue_cases import EXACT_SUM, F16, F32, F64, assert_lattice, rng_of, same_bits, to_f32_exact  # noqa: F401 (re-exported)
 
 PRIME1, PRIME2 = np.uint32(2654435761), np.uint32(805459861)  # tiny-cuda-nn's coherent-prime hash: index = x ^ y p1 ^ z p2
-SCALES = (2.0, 5.0, 11.0, 23.0, 47.0, 95.0)
+SCALES = tuple(float(3 * 2 ** lvl - 1) for lvl in range(16))  # 2, 5, 11, 23, 47, 95 and on: the field tests take up to 16 levels
 COORD_DEN = 16
 POINT_COUNTS = (0, 1, 63, 64, 65, 255, 256, 257, 4095, 4096, 4159)
 GRAD_SCALES = (1.0, 0.25, 128.0)
