@@ -91,6 +91,38 @@ def _flow_wgrad(model):
     return store.flat_grad[off:off + model.flow_net.weight_numel16()]
 
 
+def attribute_stage(model, rays_d, h, weights, idx, count, T, train):
+    """The attribute networks (lidar4d.py:191-223) on the compacted ``weights > 1e-4`` work list (idx, count) and the image
+    (renderer.py:128): the tail of ``RenderFn.forward``, and of the early-terminating march (early_stop.py), which hands in a dense
+    ``h`` whose rows behind a ray's retirement point are unwritten -- their weight is 0, so they are not in the list and never read.
+    -> image, and what the backward keeps: gathered, XA, actR, actI, attr, attr_c, denc."""
+    store = model._store
+    P = weights.numel()
+    dev = weights.device
+    denc = ops.freq_fwd(((rays_d + 1) / 2).contiguous(), model.view_encoder.n_frequencies)
+    an = model.intensity_net
+    gathered = ops.attr_mlp_supported(an.in_pad, denc.shape[1], model.geo_feat_dim) and an.n_neurons == 64
+    attr = torch.zeros(P, 2, dtype=torch.float32, device=dev)
+    attr_c = torch.empty(P, 2, dtype=torch.float32, device=dev)
+    if gathered:  # the networks assemble their input rows themselves, forward and backward (three hidden layers: the first
+        # one stores them for the backward pass), and apply the sigmoid + scatter into the dense [P, 2] image as their
+        # epilogue (lidar4d.py:210-219)
+        keep_rows = train and not ops.attr_mlp_bwd_gathered_supported(an.n_hidden_layers)
+        XA = torch.empty(P, an.in_pad, dtype=torch.float16, device=dev) if keep_rows else None
+        keep_act = train and (keep_rows or not ops.attr_mlp_recompute_supported(an.n_hidden_layers))  # else recomputed in the backward
+        _, actR = ops.attr_mlp_fwd(idx, count, P, T, denc, h, model.geo_feat_dim, an.in_pad, store.half(model.raydrop_net.params),
+                                   an.n_hidden_layers, save_act=keep_act, x_rows_out=XA, attr_dense=attr, attr_compact=attr_c, channel=0)
+        _, actI = ops.attr_mlp_fwd(idx, count, P, T, denc, h, model.geo_feat_dim, an.in_pad, store.half(model.intensity_net.params),
+                                   an.n_hidden_layers, save_act=keep_act, attr_dense=attr, attr_compact=attr_c, channel=1)
+    else:
+        XA = ops.attr_gather(idx, count, P, T, denc, h, model.geo_feat_dim, an.in_pad)
+        yR, actR = ops.mlp_fwd(XA, store.half(model.raydrop_net.params), an.n_hidden_layers, save_act=train, n_rows=count, hidden=an.n_neurons)
+        yI, actI = ops.mlp_fwd(XA, store.half(model.intensity_net.params), an.n_hidden_layers, save_act=train, n_rows=count, hidden=an.n_neurons)
+        ops.attr_scatter(idx, count, P, yR, yI, attr, attr_c)
+    image = ops.composite_image(weights, attr, 2)
+    return image, gathered, XA, actR, actI, attr, attr_c, denc
+
+
 class RenderFn(torch.autograd.Function):
     # The reference calls render() inside torch.cuda.amp.autocast (runner.py:497).  The node fixes its own precisions
     # (fp16 tables / MFMA operands, fp32 accumulation and compositing), so autocast is switched off inside it and
@@ -132,28 +164,8 @@ class RenderFn(torch.autograd.Function):
         weights, wsum, depth, _, idx, count = ops.composite_fwd(sigma, z_vals, sample_dist, model.density_scale,
                                                                 model.active_sensor, want_mask=False, want_idx=True)
 
-        # attribute (lidar4d.py:191-223) on the compacted work list
-        denc = ops.freq_fwd(((rays_d + 1) / 2).contiguous(), model.view_encoder.n_frequencies)
-        an = model.intensity_net
-        gathered = ops.attr_mlp_supported(an.in_pad, denc.shape[1], model.geo_feat_dim) and an.n_neurons == 64
-        attr = torch.zeros(P, 2, dtype=torch.float32, device=dev)
-        attr_c = torch.empty(P, 2, dtype=torch.float32, device=dev)
-        if gathered:  # the networks assemble their input rows themselves, forward and backward (three hidden layers: the first
-            # one stores them for the backward pass), and apply the sigmoid + scatter into the dense [P, 2] image as their
-            # epilogue (lidar4d.py:210-219)
-            keep_rows = train and not ops.attr_mlp_bwd_gathered_supported(an.n_hidden_layers)
-            XA = torch.empty(P, an.in_pad, dtype=torch.float16, device=dev) if keep_rows else None
-            keep_act = train and (keep_rows or not ops.attr_mlp_recompute_supported(an.n_hidden_layers))  # else recomputed in the backward
-            _, actR = ops.attr_mlp_fwd(idx, count, P, T, denc, h, model.geo_feat_dim, an.in_pad, store.half(model.raydrop_net.params),
-                                       an.n_hidden_layers, save_act=keep_act, x_rows_out=XA, attr_dense=attr, attr_compact=attr_c, channel=0)
-            _, actI = ops.attr_mlp_fwd(idx, count, P, T, denc, h, model.geo_feat_dim, an.in_pad, store.half(model.intensity_net.params),
-                                       an.n_hidden_layers, save_act=keep_act, attr_dense=attr, attr_compact=attr_c, channel=1)
-        else:
-            XA = ops.attr_gather(idx, count, P, T, denc, h, model.geo_feat_dim, an.in_pad)
-            yR, actR = ops.mlp_fwd(XA, store.half(model.raydrop_net.params), an.n_hidden_layers, save_act=train, n_rows=count, hidden=an.n_neurons)
-            yI, actI = ops.mlp_fwd(XA, store.half(model.intensity_net.params), an.n_hidden_layers, save_act=train, n_rows=count, hidden=an.n_neurons)
-            ops.attr_scatter(idx, count, P, yR, yI, attr, attr_c)
-        image = ops.composite_image(weights, attr, 2)
+        # attribute (lidar4d.py:191-223) on the compacted work list, and the image
+        image, gathered, XA, actR, actI, attr, attr_c, denc = attribute_stage(model, rays_d, h, weights, idx, count, T, train)
 
         if train:
             ctx.model, ctx.T, ctx.sample_dist, ctx.gathered = model, T, sample_dist, gathered

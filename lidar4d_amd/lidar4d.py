@@ -130,11 +130,16 @@ class LiDAR4D(LiDAR_Renderer):
             super().zero_grad(set_to_none=set_to_none)
 
     # -- fused path ------------------------------------------------------------------------------------------
-    def run(self, rays_o, rays_d, time, num_steps=768, perturb=False, noise=None, time_host=None, **kwargs):
+    def run(self, rays_o, rays_d, time, num_steps=768, perturb=False, noise=None, time_host=None, early_stop=None, slab=96, **kwargs):
         """renderer.py:44-140.  ``noise`` ([N, num_steps] in [0,1)) replaces the internal torch.rand when given
         (parity tests feed the oracle's noise).  ``time_host``: the value of ``time`` as a python float when the caller
         has it (the training loop does): spares the one device read-back of a training step -- the host-side copy of
-        hash_field.py:79-85's slice choice below, which would otherwise wait for the whole previous step to drain."""
+        hash_field.py:79-85's slice choice below, which would otherwise wait for the whole previous step to drain.
+        ``early_stop`` (a float >= 0; default None: this path, untouched) with ``slab``: a no-grad render that walks the samples
+        front to back in slabs and retires a ray once its transmittance is below ``early_stop`` (early_stop.py: the bound, and the
+        one 4-byte read-back per slab); the result gains ``evaluated_samples`` and ``retired_at``."""
+        if early_stop is not None:
+            return self._run_early_stop(rays_o, rays_d, time, num_steps, perturb, early_stop, slab)
         if not self.fused:  # four or sixteen channels per plane: sampling, density(), compositing, attribute() one after the other
             return LiDAR_Renderer.run(self, rays_o, rays_d, time, num_steps=num_steps, perturb=perturb, noise=noise)
         prefix = rays_o.shape[:-1]
@@ -168,6 +173,29 @@ class LiDAR4D(LiDAR_Renderer):
             "z_vals": z_vals,
             "mask_idx": idx,      # extra: compacted `weights > 1e-4` sample indices (renderer.py:110) ...
             "mask_count": count,  # ... and their number (device int32), the attribute work list
+        }
+
+    def _run_early_stop(self, rays_o, rays_d, time, num_steps, perturb, early_stop, slab):
+        from . import early_stop as es
+        train = False
+        if torch.is_grad_enabled() and hasattr(self, "_store"):
+            train = any(p.requires_grad for _, p, _, n, _ in self._store.entries if n > 0)
+        eps, S = es.check_options(self, early_stop, slab, perturb, train)
+        prefix = rays_o.shape[:-1]
+        rays_o = rays_o.contiguous().view(-1, 3).float()
+        rays_d = rays_d.contiguous().view(-1, 3).float()
+        depth, image, wsum, weights, z_vals, idx, count, evaluated, retired_at = es.run(
+            self, rays_o, rays_d, _t_device(time, rays_o.device), num_steps, eps, S)
+        return {
+            "depth_lidar": depth.view(*prefix),
+            "image_lidar": image.view(*prefix, self.out_lidar_dim),
+            "weights_sum_lidar": wsum,
+            "weights": weights,
+            "z_vals": z_vals,
+            "mask_idx": idx,
+            "mask_count": count,
+            "evaluated_samples": evaluated,  # density rows actually computed (device int64 scalar), of N * num_steps
+            "retired_at": retired_at,        # [N] int32: samples evaluated per ray
         }
 
     # -- operator-level API (lidar4d.py:124-223) -----------------------------------------------------------

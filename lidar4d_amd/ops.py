@@ -487,10 +487,13 @@ def time_setup(t_dev, num_frames, tinfo=None):
     return tinfo
 
 
-def density_encode_fwd(field_desc, xt, flow16, tinfo, in_pad, X=None, sigma_weights16=None, n_hidden=0, save_act=True):
+def density_encode_fwd(field_desc, xt, flow16, tinfo, in_pad, X=None, sigma_weights16=None, n_hidden=0, save_act=True, rows_like_points=None):
     """-> X [P, in_pad] fp16.  With ``sigma_weights16`` (the density network's fp16 weights): -> (X, y [P,16] fp16, act or None,
     sigma [P] fp32) = the rows AND ``mlp_fwd_sigma`` of them in one call (l4d_density_encode_sigma_fwd: for the default network
-    shape the network runs inside the encode kernel)."""
+    shape the network runs inside the encode kernel).
+    rows_like_points: take the time planes' form (1-D rows and two taps, or four taps) a batch of that many points would take
+    instead of P's: the two round differently (one fp16 unit in a few plane columns), and the slabs of an early-terminating
+    march (early_stop.py) are pieces of one batch."""
     _chk(xt, torch.float32, "xt"), _chk(flow16, torch.float16, "flow16"), _chk(tinfo, torch.float32, "tinfo")
     P = xt.shape[0]
     if X is None:
@@ -500,7 +503,7 @@ def density_encode_fwd(field_desc, xt, flow16, tinfo, in_pad, X=None, sigma_weig
                                            field_desc.hash_dynamic[2].size[field_desc.hash_dynamic[2].n_levels - 1]) <= 8192:
         scratch = torch.empty(_lib.lib().l4d_density_encode_fwd_workspace(C.byref(field_desc), P), dtype=torch.uint8, device=xt.device)
     rows = None
-    if P >= PLANE_ROWS_MIN_POINTS:  # time planes through per-call 1-D rows (two taps instead of four)
+    if (P if rows_like_points is None else rows_like_points) >= PLANE_ROWS_MIN_POINTS:  # time planes through per-call 1-D rows (two taps instead of four)
         rows = torch.empty(_lib.lib().l4d_plane_rows_workspace(C.byref(field_desc)) // 4, dtype=torch.float32, device=xt.device)
     if sigma_weights16 is not None:
         _chk(sigma_weights16, torch.float16, "sigma weights")

@@ -83,6 +83,8 @@ class LiDAR_Renderer(nn.Module):
 
     def run(self, rays_o, rays_d, time, num_steps=768, perturb=False, noise=None, **kwargs):
         """Generic (un-fused) run for subclasses that only define density()/attribute()."""
+        if kwargs.get("early_stop") is not None:
+            raise ValueError("early_stop needs the fused pipeline (LiDAR4D with model.fused): this run evaluates every sample")
         prefix = rays_o.shape[:-1]
         rays_o = rays_o.contiguous().view(-1, 3).float()
         rays_d = rays_d.contiguous().view(-1, 3).float()
@@ -153,7 +155,11 @@ class LiDAR_Renderer(nn.Module):
             # (a model without the fused pipeline reads the time on the host in density(): nothing to capture)
             graphed = (self.graph_staged and getattr(self, "fused", True) and device.type == "cuda" and not torch.is_grad_enabled() and hasattr(self, "_store")
                        and not kwargs.get("perturb", False) and kwargs.get("noise") is None and torch.is_tensor(time)
-                       and time.device == device)
+                       and time.device == device
+                       and kwargs.get("early_stop") is None)  # (a march reads one count per slab on the host: never captured)
+            marched = kwargs.get("early_stop") is not None    # its two extra keys, over the whole frame
+            retired_at = torch.empty((B, N), dtype=torch.int32, device=device) if marched else None
+            evaluated = 0
             for b in range(B):
                 head = 0
                 while head < N:
@@ -167,6 +173,11 @@ class LiDAR_Renderer(nn.Module):
                     r = _run(rays_o[b:b + 1, head:tail], rays_d[b:b + 1, head:tail], time[b:b + 1], **kwargs)
                     depth[b:b + 1, head:tail] = r["depth_lidar"]
                     image[b:b + 1, head:tail] = r["image_lidar"]
+                    if marched:
+                        retired_at[b, head:tail] = r["retired_at"]
+                        evaluated = evaluated + r["evaluated_samples"]
                     head += max_ray_batch
+            if marched:
+                return {"depth_lidar": depth, "image_lidar": image, "evaluated_samples": evaluated, "retired_at": retired_at}
             return {"depth_lidar": depth, "image_lidar": image}
         return _run(rays_o, rays_d, time, **kwargs)

@@ -876,6 +876,11 @@ class GradReducer:
             self._finish16()
 
 
+def _march_kw(early_stop, slab):
+    """The render keywords of an early-terminating march; none at all when it is not asked for (the plain render's call)."""
+    return {} if early_stop is None else {"early_stop": early_stop, "slab": slab}
+
+
 class Trainer:
     """One process per GPU.  Rays (whole frames) are sharded across ranks -- each rank draws its own frame and ray
     indices -- parameters are replicated and the flat gradient buffer is SUM-all-reduced once per step (the primary
@@ -1195,10 +1200,10 @@ class Trainer:
             self.ema.update()
 
     @torch.no_grad()
-    def collect_refine_data(self, dataset=None, frames=None, max_ray_batch=4096):
+    def collect_refine_data(self, dataset=None, frames=None, max_ray_batch=4096, early_stop=None, slab=96):
         """runner.py:824-863: render every frame of ``dataset`` (the reference's ``refine`` split: the training frames served
         whole; default: the trainer's own dataset) with the (frozen) field and stack what the U-Net sees --
-        returns (raydrop_input [B, 3, H, W], raydrop_gt [B, 1, H, W]) for ``refine_unet``."""
+        returns (raydrop_input [B, 3, H, W], raydrop_gt [B, 1, H, W]) for ``refine_unet``.  early_stop / slab: ``test_step``'s."""
         dataset = self.dataset if dataset is None else dataset
         self.model.eval()
         if self.ema is not None:
@@ -1208,21 +1213,23 @@ class Trainer:
             fr = dataset.frame(k)
             H, W = fr["H_lidar"], fr["W_lidar"]
             out = self.model.render(fr["rays_o_lidar"], fr["rays_d_lidar"], fr["time"], staged=True, perturb=False,
-                                    max_ray_batch=max_ray_batch, num_steps=self.num_steps)
+                                    max_ray_batch=max_ray_batch, num_steps=self.num_steps, **_march_kw(early_stop, slab))
             image = out["image_lidar"].reshape(-1, H, W, 2)
             inputs.append(torch.cat([image[..., 0], image[..., 1], out["depth_lidar"].reshape(-1, H, W)], dim=0).unsqueeze(0))
             gts.append(fr["images_lidar"][:, :, :, 0].unsqueeze(0))
         return torch.cat(inputs, 0).float().contiguous(), torch.cat(gts, 0).float().contiguous()
 
     @torch.no_grad()
-    def test_step(self, data, refine=True, perturb=False, max_ray_batch=4096, raydrop_loss="mse", alpha_r=0.01):
+    def test_step(self, data, refine=True, perturb=False, max_ray_batch=4096, raydrop_loss="mse", alpha_r=0.01, early_stop=None, slab=96):
         """runner.py:438-470: render every ray of a frame in chunks (staged), refine the ray-drop probability with the
         U-Net on the stacked [ray-drop, intensity, depth] image, mask intensity and depth by ray-drop > 0.5.
         data: ``rays_o_lidar``/``rays_d_lidar`` [B, H*W, 3], ``time`` [B,1], ``H_lidar``, ``W_lidar``.
-        Returns (pred_raydrop [1,H,W], pred_intensity [B,H,W], pred_depth [B,H,W])."""
+        Returns (pred_raydrop [1,H,W], pred_intensity [B,H,W], pred_depth [B,H,W]).
+        early_stop (default None: every sample of every ray) / slab: handed to ``model.render`` -- rays are retired once their
+        transmittance is below ``early_stop``, tested every ``slab`` samples (lidar4d_amd/early_stop.py has the bound)."""
         H, W = data["H_lidar"], data["W_lidar"]
         out = self.model.render(data["rays_o_lidar"], data["rays_d_lidar"], data["time"], staged=True, perturb=perturb,
-                                max_ray_batch=max_ray_batch, num_steps=self.num_steps)
+                                max_ray_batch=max_ray_batch, num_steps=self.num_steps, **_march_kw(early_stop, slab))
         image = out["image_lidar"].reshape(-1, H, W, 2)
         pred_raydrop, pred_intensity = image[..., 0], image[..., 1]
         pred_depth = out["depth_lidar"].reshape(-1, H, W)
@@ -1239,7 +1246,7 @@ class Trainer:
 
     @torch.no_grad()
     def evaluate(self, dataset=None, frames=None, refine=True, max_ray_batch=4096, raydrop_loss="mse", intensity_scale=1.0, raydrop_ratio=0.5,
-                 lpips_fn=None):
+                 lpips_fn=None, early_stop=None, slab=96):
         """runner.py:379-434,553-682 without the PNG, progress-bar and tensorboard output: every frame (default: all) of
         ``dataset`` (default: the trainer's own; the reference evaluates its ``val`` split) is rendered on the EMA weights if there are any, scored by the evaluation loss of runner.py:418-422 (the
         trainer's criteria, the reference's default weights 1 / 0.01 / 0.1) and fed to the four meters of
@@ -1267,7 +1274,8 @@ class Trainer:
             for k in (dataset_frames(dataset) if frames is None else frames):
                 fr = dataset.frame(k)
                 pred_raydrop, pred_intensity, pred_depth = self.test_step(fr, refine=refine, max_ray_batch=max_ray_batch,
-                                                                          raydrop_loss=raydrop_loss, alpha_r=0)  # unmasked
+                                                                          raydrop_loss=raydrop_loss, alpha_r=0,  # unmasked
+                                                                          early_stop=early_stop, slab=slab)
                 images = fr["images_lidar"].float()  # (fp16 ground truth widens exactly; the mask is 0 / 1)
                 gt_raydrop = images[:, :, :, 0]
                 gt_intensity = images[:, :, :, 1] * gt_raydrop
