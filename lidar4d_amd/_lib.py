@@ -14,6 +14,10 @@ L4D_MAX_TIME_SLICES = 8
 L4D_MAX_PLANE_SCALES = 8
 ABI_VERSION = 4
 
+# The binding modules of the package, one per shared library, in load order: this one (mapped with the package), then those mapped on
+# first use.  Names only -- importing them here would import every library's host side with the package.
+BINDINGS = ("_lib", "_prep_lib", "_eval_lib", "_loss_lib", "_patch_lib", "_step_lib", "_mlp_lib", "_planes_lib", "_march_lib")
+
 
 class GridDesc(C.Structure):
     _fields_ = [

@@ -8,6 +8,7 @@
 // This is the direct-gather formulation (every table entry is fetched through L1/L2).
 #include "field_dev.h"
 #include "mlp_dev.h"
+#include "render_dev.h"
 #include <algorithm>
 #include <type_traits>
 
@@ -643,9 +644,7 @@ __global__ void __launch_bounds__(256) sample_rays_xt_kernel(const float* __rest
   float4_t o;
 #pragma unroll
   for (int k = 0; k < 3; ++k) {
-    float v = rays_o[ray * 3 + k] + rays_d[ray * 3 + k] * z;
-    v = fminf(fmaxf(v, -bound), bound);          // renderer.py:89
-    o[k] = (v + bound) / (2.0f * bound);         // lidar4d.py:141
+    o[k] = unit_coord(ray_point(rays_o[ray * 3 + k], rays_d[ray * 3 + k], z, bound), bound);
   }
   o[3] = *t;
   *reinterpret_cast<float4_t*>(xt + idx * 4) = o;

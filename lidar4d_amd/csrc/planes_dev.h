@@ -1,5 +1,6 @@
 // Device functions of the hex-plane bilinear sampler (ATen grid_sampler_2d semantics: bilinear,
-// align_corners=True, border padding), shared by planes.hip and fused.hip.
+// align_corners=True, border padding), shared by fused.hip, field_bwd.hip and the un-fused kernels of planes_kernels.h
+// (planes.hip, planes_width.hip).
 #pragma once
 #include "common.h"
 

@@ -2,15 +2,17 @@
 //
 // A no-grad render with early_stop = eps walks every ray front to back in slabs of S samples (lidar4d_amd/early_stop.py).  The field
 // and the networks of a slab are liblidar4d_hip.so's kernels on compact rows (live rays only); here are
-//   slab_rows_kernel    the (x, y, z, t) rows of the live rays' samples of one slab: sample_rays_xt_kernel's expression (csrc/fused.hip)
-//                       without noise, bit for bit (this file is compiled with the same -ffp-contract=off);
+//   slab_rows_kernel    the (x, y, z, t) rows of the live rays' samples of one slab: sample_rays_xt_kernel's (csrc/fused.hip) without
+//                       noise, through the same two functions of render_dev.h;
 //   slab_update_kernel  one wavefront per live ray: sigma and the 16-column fp16 rows from the compact buffers to their dense places,
-//                       the slab's transmittance factors multiplied in a fixed order (lane products, then a shuffle tree), retirement,
+//                       the slab's transmittance factors (composite_fwd_kernel's alpha: render_dev.h's alpha_of) multiplied in a fixed
+//                       order (lane products, then a shuffle tree), retirement,
 //                       zeros for the retired ray's remaining sigma, one flag per live ray;
 //   slab_compact_kernel the flags to the next slab's live list, in order and without atomics (the ballot ranking of csrc/convert.hip;
 //                       one workgroup: a list is at most one ray batch long and the pass is a few microseconds).
 // No floating-point atomics anywhere: two calls give the same bits and the same order.
 #include "common.h"
+#include "render_dev.h"
 #include "wave_dev.h"
 
 #include "../../include/lidar4d_march.h"
@@ -47,18 +49,10 @@ __global__ void __launch_bounds__(256) slab_rows_kernel(const float* __restrict_
   float4_t o;
 #pragma unroll
   for (int k = 0; k < 3; ++k) {
-    float v = rays_o[ray * 3 + k] + rays_d[ray * 3 + k] * z;
-    v = fminf(fmaxf(v, -bound), bound);          // renderer.py:89
-    o[k] = (v + bound) / (2.0f * bound);         // lidar4d.py:141
+    o[k] = unit_coord(ray_point(rays_o[ray * 3 + k], rays_d[ray * 3 + k], z, bound), bound);
   }
   o[3] = *t;
   *reinterpret_cast<float4_t*>(xt + idx * 4) = o;
-}
-
-// render.hip's alpha_of: 1 - exp(-deltas * density_scale * sigma)  /  1 - exp(-2 * deltas * density_scale * sigma)
-__device__ __forceinline__ float march_alpha(float delta, float sigma, float density_scale, int active) {
-  float e = active ? ((-2.0f * delta) * density_scale) * sigma : ((-delta) * density_scale) * sigma;
-  return 1.0f - expf(e);
 }
 
 __global__ void __launch_bounds__(64 * RM_RAYS) slab_update_kernel(const float* __restrict__ sigma_c, const uint4* __restrict__ h_c,
@@ -81,7 +75,7 @@ __global__ void __launch_bounds__(64 * RM_RAYS) slab_update_kernel(const float* 
     const float sgm = sg[k];
     sd[s] = sgm;
     const float delta = (s + 1 < T) ? (zv[s + 1] - zv[s]) : sample_dist;
-    const float f = (1.0f - march_alpha(delta, sgm, density_scale, active)) + 1e-15f;
+    const float f = (1.0f - alpha_of(delta, sgm, density_scale, active)) + 1e-15f;
     p = k == lane ? f : p * f;
   }
   // the slab's h rows are contiguous on both sides: Sp * 32 bytes as 16-byte words

@@ -7,6 +7,7 @@
 // `weights > 1e-4` test is compacted with ballots (wave-level compaction): lanes write their surviving sample indices
 // into a slot range reserved by ONE atomicAdd per ray.
 #include "common.h"
+#include "render_dev.h"
 
 #define MAXC 16  // samples per lane per segment -> segments of 1024 samples
 
@@ -58,20 +59,12 @@ __global__ void __launch_bounds__(256) sample_rays_kernel(const float* __restric
   if (xyz) {
 #pragma unroll
     for (int k = 0; k < 3; ++k) {
-      float v = rays_o[ray * 3 + k] + rays_d[ray * 3 + k] * z;
-      v = fminf(fmaxf(v, -bound), bound);
-      xyz[idx * 3 + k] = v;
+      xyz[idx * 3 + k] = ray_point(rays_o[ray * 3 + k], rays_d[ray * 3 + k], z, bound);
     }
   }
 }
 
 // ---- compositing forward (renderer.py:98-110,121-126) ------------------------------------------
-__device__ __forceinline__ float alpha_of(float delta, float sigma, float density_scale, int active) {
-  // 1 - exp(-deltas * density_scale * sigma)  /  1 - exp(-2 * deltas * density_scale * sigma)
-  float e = active ? ((-2.0f * delta) * density_scale) * sigma : ((-delta) * density_scale) * sigma;
-  return 1.0f - expf(e);
-}
-
 #define CF_RAYS 16  // rays (wavefronts) per workgroup of composite_fwd_kernel
 __global__ void __launch_bounds__(64 * CF_RAYS) composite_fwd_kernel(const float* __restrict__ sigma, const float* __restrict__ z_vals,
                                                            int64_t N, int T, float sample_dist, float density_scale,

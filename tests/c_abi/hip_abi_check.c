@@ -1,6 +1,6 @@
 /* Plain-C consumer of include/lidar4d_hip.h: proves that the header is valid C (no C++ or torch types in the boundary),
  * that every declared entry point links against liblidar4d_hip.so with the declared prototype, and that the version and
- * error calls work without a GPU.  Built and run by tests/test_host_logic.py::test_c_abi_from_plain_c (gcc). */
+ * error calls work without a GPU.  Built and run by tests/test_abi_cpu.py::test_c_abi_from_plain_c[hip] (gcc). */
 #include <stdio.h>
 
 #include "lidar4d_hip.h"

@@ -1,6 +1,6 @@
 /* Plain-C consumer of include/lidar4d_patch.h: proves that the header is valid C (no C++ or torch types in the boundary),
  * that every declared entry point links against liblidar4d_patch.so with the declared prototype, and that the version and
- * error calls work without a GPU.  Built and run by tests/test_patchgrad_cpu.py::test_patch_c_abi_from_plain_c (gcc). */
+ * error calls work without a GPU.  Built and run by tests/test_abi_cpu.py::test_c_abi_from_plain_c[patch] (gcc). */
 #include <stdio.h>
 #include <string.h>
 

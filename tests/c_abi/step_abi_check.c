@@ -1,6 +1,6 @@
 /* Plain-C consumer of include/lidar4d_step.h: proves that the header is valid C (no C++ or torch types in the boundary),
  * that every declared entry point links against liblidar4d_step.so with the declared prototype, and that the version, error
- * and argument checks work without a GPU.  Built and run by tests/test_realdata_cpu.py::test_step_c_abi_from_plain_c (gcc). */
+ * and argument checks work without a GPU.  Built and run by tests/test_abi_cpu.py::test_c_abi_from_plain_c[step] (gcc). */
 #include <stdio.h>
 #include <string.h>
 

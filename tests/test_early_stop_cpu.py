@@ -1,5 +1,4 @@
-"""CPU side of early ray termination (``render(..., early_stop=eps, slab=S)``): the ninth shared object (liblidar4d_march.so,
-include/lidar4d_march.h) passes the four C ABI checks of tests/test_abi_cpu.py and shares no export with the other eight; what the
+"""CPU side of early ray termination (``render(..., early_stop=eps, slab=S)``): what the
 option cannot do is refused by name before anything touches a device; without the option the render goes through the same function
 as before (``RenderFn.apply``); the numpy restatement of the retirement rule (tests/early_stop_ref.py) is pinned; and on the CPU oracle
 the scenes the GPU tests use retire rays where they are said to, with the culled weights inside the bound.  No GPU."""
@@ -14,16 +13,6 @@ import test_abi_cpu as abi
 from oracle import fields_ref
 from oracle.detparams import fill_model
 from oracle.make_golden import SMALL_MODEL, test_rays as make_rays
-
-MARCH = abi.Library(binding="_march_lib", header="lidar4d_march.h", prefix="l4dr_", c_file="march_abi_check.c", link="lidar4d_march",
-                    abi=1, names={"l4dr_march_init", "l4dr_slab_rows", "l4dr_slab_update_workspace", "l4dr_slab_update"},
-                    stream_last=True,
-                    first_use="import lidar4d_amd, lidar4d_amd.trainer, lidar4d_amd.simulator, lidar4d_amd.ops, lidar4d_amd.early_stop, sys\n"
-                              "assert 'lidar4d_amd._march_lib' not in sys.modules\n"
-                              "from oracle.make_golden import SMALL_MODEL\n"
-                              "lidar4d_amd.LiDAR4D(**SMALL_MODEL)\n"  # neither the package, the march's host side nor a model maps it
-                              "assert 'lidar4d_amd._march_lib' not in sys.modules\n"
-                              "from lidar4d_amd import _march_lib as binding\n")
 
 # The scenes (tests/test_gpu_early_stop.py renders the same ones): SMALL_MODEL, fill_model(seed=7), make_rays(64, 36), t = 0.5,
 # T = 96, S = 16.  MIXED: row 0 of the density network's output matrix (the one that makes sigma) times G, with the density_scale that
@@ -69,42 +58,14 @@ def oracle_render(density_scale, g):
     return _ORACLE[key]
 
 
-# ---- the ninth shared object (the checks: tests/test_abi_cpu.py) -----------------------------------------------------------
-def test_march_library_exports_declared_abi():
-    abi.check_exports_declared_abi(MARCH)
-
-
+# Kept under their earlier names, as calls of the checks in tests/test_abi_cpu.py, which run there for every library: a new library
+# adds no test of this kind.
 def test_march_ctypes_signatures_match_header_prototypes():
-    abi.check_ctypes_signatures_match_header_prototypes(MARCH)
-
-
-def test_march_c_abi_from_plain_c(tmp_path):
-    abi.check_c_abi_from_plain_c(MARCH, tmp_path)
-
-
-def test_march_library_is_loaded_on_first_use_only():
-    abi.check_loaded_on_first_use_only(MARCH)
+    abi.test_ctypes_signatures_match_header_prototypes(abi.ROW["march"])
 
 
 def test_march_library_exports_no_name_of_another():
-    import test_mlp_width_cpu
-    import test_patchgrad_cpu
-    import test_planes_width_cpu
-    import test_realdata_cpu
-    mine = abi._exported(abi._binding(MARCH).LIB_PATH)
-    assert mine
-    others = abi.LIBRARIES + [test_patchgrad_cpu.PATCH, test_realdata_cpu.STEP, test_mlp_width_cpu.MLP, test_planes_width_cpu.PLANES]
-    assert len(others) == 8
-    for row in others:
-        abi._require_built(row, abi._binding(row))
-        theirs = abi._exported(abi._binding(row).LIB_PATH)
-        assert not mine & theirs, (row.link, sorted(mine & theirs)[:8])
-
-
-def test_build_checks_the_march_library():
-    import inspect
-    import __graft_entry__ as entry
-    assert "_march_lib" in inspect.getsource(entry.build)
+    abi.test_no_library_exports_a_name_of_another()
 
 
 # ---- refusals that need no device --------------------------------------------------------------------------------------------

@@ -1,27 +1,8 @@
 """CPU tests of the fused line-of-sight loss (lidar4d_amd.trainer.line_of_sight_loss, include/lidar4d_loss.h): the fourth shared
-object's ABI and its loading on first use (the checks of tests/test_abi_cpu.py), its argument checks, the absence of a CPU path, and that a
+object's argument checks (its C ABI: tests/test_abi_cpu.py), the absence of a CPU path, and that a
 Trainer without ``fused_urf`` keeps the torch route (tests/test_gpu_los.py compares the kernels with it)."""
 import pytest
 import torch
-
-import test_abi_cpu as abi
-
-
-# ---- the fourth shared object (the checks: tests/test_abi_cpu.py) ---------------------------------------------------------------
-def test_loss_library_exports_declared_abi():
-    abi.check_exports_declared_abi(abi.LOSS)
-
-
-def test_loss_ctypes_signatures_match_header_prototypes():
-    abi.check_ctypes_signatures_match_header_prototypes(abi.LOSS)
-
-
-def test_loss_c_abi_from_plain_c(tmp_path):
-    abi.check_c_abi_from_plain_c(abi.LOSS, tmp_path)
-
-
-def test_loss_library_is_loaded_on_first_use_only():
-    abi.check_loaded_on_first_use_only(abi.LOSS)
 
 
 def test_workspace_and_argument_checks_need_no_device():

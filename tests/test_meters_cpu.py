@@ -1,5 +1,5 @@
 """CPU tests of the evaluation meters (lidar4d_amd/metrics.py DepthMeter / IntensityMeter, include/lidar4d_eval.h): the third
-shared object's ABI (the checks of tests/test_abi_cpu.py) and argument checks, the absence of a CPU path, and the numpy restatements
+shared object's argument checks (its C ABI: tests/test_abi_cpu.py), the absence of a CPU path, and the numpy restatements
 tests/test_gpu_meters.py compares the kernels with (tests/meters_ref.py): the float64 formula against plain loops and against the
 reference's own float32 arithmetic."""
 import numpy as np
@@ -7,24 +7,6 @@ import pytest
 import torch
 
 import meters_ref as ref
-import test_abi_cpu as abi
-
-
-# ---- the third shared object (the checks: tests/test_abi_cpu.py) ---------------------------------------------------------------
-def test_eval_library_exports_declared_abi():
-    abi.check_exports_declared_abi(abi.EVAL)
-
-
-def test_eval_ctypes_signatures_match_header_prototypes():
-    abi.check_ctypes_signatures_match_header_prototypes(abi.EVAL)
-
-
-def test_eval_c_abi_from_plain_c(tmp_path):
-    abi.check_c_abi_from_plain_c(abi.EVAL, tmp_path)
-
-
-def test_eval_library_is_loaded_on_first_use_only():
-    abi.check_loaded_on_first_use_only(abi.EVAL)
 
 
 def test_workspace_and_argument_checks_need_no_device():

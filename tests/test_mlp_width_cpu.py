@@ -1,6 +1,5 @@
-"""CPU side of the hidden widths 16, 32 and 128: the integer lattice of tests/mlp_width_ref.py is exact for all 72 shapes, the
-seventh shared object (liblidar4d_mlp.so, include/lidar4d_mlp.h) passes the four C ABI checks of tests/test_abi_cpu.py and shares
-no export with the other six, ``tcnn.Network`` has the oracle's parameter count and layer shapes at every width, and a model of
+"""CPU side of the hidden widths 16, 32 and 128: the integer lattice of tests/mlp_width_ref.py is exact for all 72 shapes,
+``tcnn.Network`` has the oracle's parameter count and layer shapes at every width, and a model of
 mixed widths constructs, has the oracle's state-dict keys and shapes and survives a checkpoint round trip.  No GPU."""
 import numpy as np
 import pytest
@@ -9,15 +8,6 @@ import torch
 import mlp_width_ref as mw
 import test_abi_cpu as abi
 
-MLP = abi.Library(binding="_mlp_lib", header="lidar4d_mlp.h", prefix="l4dm_", c_file="mlp_abi_check.c", link="lidar4d_mlp", abi=1,
-                  names={"l4dm_mlp_fwd", "l4dm_mlp_bwd"}, stream_last=True,
-                  first_use="import lidar4d_amd, lidar4d_amd.trainer, lidar4d_amd.ops, lidar4d_amd.tcnn, sys\n"
-                            "assert 'lidar4d_amd._mlp_lib' not in sys.modules\n"
-                            "from oracle.make_golden import SMALL_MODEL\n"
-                            "lidar4d_amd.LiDAR4D(**SMALL_MODEL)\n"  # a model of the default widths does not touch it,
-                            "lidar4d_amd.LiDAR4D(**dict(SMALL_MODEL, hidden_dim_sigma=32, hidden_dim_lidar=128, hidden_dim_flow=16))\n"
-                            "assert 'lidar4d_amd._mlp_lib' not in sys.modules\n"  # and constructing one of other widths does not either
-                            "from lidar4d_amd import _mlp_lib as binding\n")
 MIXED = dict(hidden_dim_sigma=32, hidden_dim_lidar=128, hidden_dim_flow=16)
 
 
@@ -40,32 +30,14 @@ def test_lattice_is_exact_at_the_grid_stride_row_count(hidden):
         mw.Case(hidden, 96, 2, P).stats_ok()
 
 
-# ---- the seventh shared object (the checks: tests/test_abi_cpu.py) ---------------------------------------------------------
-def test_mlp_library_exports_declared_abi():
-    abi.check_exports_declared_abi(MLP)
-
-
+# Kept under their earlier names, as calls of the checks in tests/test_abi_cpu.py, which run there for every library: a new library
+# adds no test of this kind.
 def test_mlp_ctypes_signatures_match_header_prototypes():
-    abi.check_ctypes_signatures_match_header_prototypes(MLP)
-
-
-def test_mlp_c_abi_from_plain_c(tmp_path):
-    abi.check_c_abi_from_plain_c(MLP, tmp_path)
-
-
-def test_mlp_library_is_loaded_on_first_use_only():
-    abi.check_loaded_on_first_use_only(MLP)
+    abi.test_ctypes_signatures_match_header_prototypes(abi.ROW["mlp"])
 
 
 def test_mlp_library_exports_no_name_of_another():
-    import test_patchgrad_cpu
-    import test_realdata_cpu
-    mine = abi._exported(abi._binding(MLP).LIB_PATH)
-    assert mine
-    for row in abi.LIBRARIES + [test_patchgrad_cpu.PATCH, test_realdata_cpu.STEP]:
-        abi._require_built(row, abi._binding(row))
-        theirs = abi._exported(abi._binding(row).LIB_PATH)
-        assert not mine & theirs, (row.link, sorted(mine & theirs)[:8])
+    abi.test_no_library_exports_a_name_of_another()
 
 
 # ---- modules ----------------------------------------------------------------------------------------------------------------

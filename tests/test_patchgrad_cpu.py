@@ -1,6 +1,5 @@
 """CPU tests of the fused patch depth-gradient loss (lidar4d_amd.trainer.patch_depth_grad_loss, include/lidar4d_patch.h): the
-fifth shared object's ABI and its loading on first use (the checks of tests/test_abi_cpu.py on a row built here), its argument
-checks, the absence of a CPU path, that a Trainer without ``fused_patch`` keeps the torch route, the patch-epoch schedule, and
+fifth shared object's argument checks (its C ABI: tests/test_abi_cpu.py), the absence of a CPU path, that a Trainer without ``fused_patch`` keeps the torch route, the patch-epoch schedule, and
 that the shared case generator (tests/patchgrad_cases.py) makes the cases tests/test_gpu_patchgrad.py relies on."""
 import itertools
 
@@ -10,37 +9,15 @@ import torch
 import patchgrad_cases as pc
 import test_abi_cpu as abi
 
-PATCH = abi.Library(binding="_patch_lib", header="lidar4d_patch.h", prefix="l4dg_", c_file="patch_abi_check.c", link="lidar4d_patch",
-                    abi=1, names={"l4dg_patch_workspace", "l4dg_patch_fwd", "l4dg_patch_bwd"}, stream_last=True,
-                    first_use="import lidar4d_amd, lidar4d_amd.trainer\n"
-                              "from lidar4d_amd import _patch_lib as binding\n"
-                              "assert callable(lidar4d_amd.trainer.patch_depth_grad_loss)\n")
 
-
-# ---- the fifth shared object (the checks: tests/test_abi_cpu.py) ----------------------------------------------------------------
-def test_patch_library_exports_declared_abi():
-    abi.check_exports_declared_abi(PATCH)
-
-
+# Kept under their earlier names, as calls of the checks in tests/test_abi_cpu.py, which run there for every library: a new library
+# adds no test of this kind.
 def test_patch_ctypes_signatures_match_header_prototypes():
-    abi.check_ctypes_signatures_match_header_prototypes(PATCH)
-
-
-def test_patch_c_abi_from_plain_c(tmp_path):
-    abi.check_c_abi_from_plain_c(PATCH, tmp_path)
-
-
-def test_patch_library_is_loaded_on_first_use_only():
-    abi.check_loaded_on_first_use_only(PATCH)
+    abi.test_ctypes_signatures_match_header_prototypes(abi.ROW["patch"])
 
 
 def test_patch_library_exports_no_name_of_another():
-    mine = abi._exported(abi._binding(PATCH).LIB_PATH)
-    assert mine
-    for row in abi.LIBRARIES:
-        abi._require_built(row, abi._binding(row))
-        theirs = abi._exported(abi._binding(row).LIB_PATH)
-        assert not mine & theirs, (row.link, sorted(mine & theirs)[:8])
+    abi.test_no_library_exports_a_name_of_another()
 
 
 def test_workspace_and_argument_checks_need_no_device():

@@ -1,5 +1,4 @@
-"""CPU side of the hex-plane widths 4 and 16: the eighth shared object (liblidar4d_planes.so, include/lidar4d_planes.h) passes the
-four C ABI checks of tests/test_abi_cpu.py and shares no export with the other seven; the float64 yardstick of
+"""CPU side of the hex-plane widths 4 and 16 (liblidar4d_planes.so; its C ABI checks are tests/test_abi_cpu.py's): the float64 yardstick of
 tests/planes_width_ref.py agrees with oracle/fields_ref.py composed as ``fields_ref.LiDAR4D.density`` composes it (so that it is
 pinned before tests/test_gpu_planes_width.py lets it judge a kernel); ``LiDAR4D(n_features_per_level_plane = 4 / 16)`` constructs
 with the oracle's state-dict keys and shapes, without the fused pipeline, and what cannot run is refused by name.  No GPU."""
@@ -12,47 +11,18 @@ from oracle import fields_ref
 from oracle.detparams import det_uniform
 from oracle.make_golden import SMALL_MODEL
 
-PLANES = abi.Library(binding="_planes_lib", header="lidar4d_planes.h", prefix="l4dh_", c_file="planes_abi_check.c", link="lidar4d_planes",
-                     abi=1, names={"l4dh_planes_fwd", "l4dh_planes_bwd", "l4dh_density_planes_fwd", "l4dh_density_planes_bwd"},
-                     stream_last=True,
-                     first_use="import lidar4d_amd, lidar4d_amd.trainer, lidar4d_amd.ops, lidar4d_amd.planes_field, sys\n"
-                               "assert 'lidar4d_amd._planes_lib' not in sys.modules\n"
-                               "from oracle.make_golden import SMALL_MODEL\n"
-                               "lidar4d_amd.LiDAR4D(**SMALL_MODEL)\n"  # a model of the default width does not touch it,
-                               "lidar4d_amd.LiDAR4D(**dict(SMALL_MODEL, n_features_per_level_plane=16))\n"
-                               "assert 'lidar4d_amd._planes_lib' not in sys.modules\n"  # and constructing one of another width does not either
-                               "from lidar4d_amd import _planes_lib as binding\n")
 CFG4 = dict(SMALL_MODEL, n_features_per_level_plane=4, n_levels_plane=4)  # 2 * 4 * 4 + 28 = 60 -> 64 columns
 CFG16 = dict(SMALL_MODEL, n_features_per_level_plane=16)                  # 2 * 2 * 16 + 28 = 92 -> 96 columns
 
 
-# ---- the eighth shared object (the checks: tests/test_abi_cpu.py) ----------------------------------------------------------
-def test_planes_library_exports_declared_abi():
-    abi.check_exports_declared_abi(PLANES)
-
-
+# Kept under their earlier names, as calls of the checks in tests/test_abi_cpu.py, which run there for every library: a new library
+# adds no test of this kind.
 def test_planes_ctypes_signatures_match_header_prototypes():
-    abi.check_ctypes_signatures_match_header_prototypes(PLANES)
-
-
-def test_planes_c_abi_from_plain_c(tmp_path):
-    abi.check_c_abi_from_plain_c(PLANES, tmp_path)
-
-
-def test_planes_library_is_loaded_on_first_use_only():
-    abi.check_loaded_on_first_use_only(PLANES)
+    abi.test_ctypes_signatures_match_header_prototypes(abi.ROW["planes"])
 
 
 def test_planes_library_exports_no_name_of_another():
-    import test_mlp_width_cpu
-    import test_patchgrad_cpu
-    import test_realdata_cpu
-    mine = abi._exported(abi._binding(PLANES).LIB_PATH)
-    assert mine
-    for row in abi.LIBRARIES + [test_patchgrad_cpu.PATCH, test_realdata_cpu.STEP, test_mlp_width_cpu.MLP]:
-        abi._require_built(row, abi._binding(row))
-        theirs = abi._exported(abi._binding(row).LIB_PATH)
-        assert not mine & theirs, (row.link, sorted(mine & theirs)[:8])
+    abi.test_no_library_exports_a_name_of_another()
 
 
 # ---- the float64 yardstick against the oracle ------------------------------------------------------------------------------

@@ -1,7 +1,6 @@
 """CPU tests of the point-cloud preparation (lidar4d_amd/pointprep.py, include/lidar4d_prep.h): the numpy restatement
 (tests/pointprep_ref.py) against the fixture the reference's own functions wrote, the product's host-side RANSAC replay against
-the same fixture (stream consumption and the K logic, without a GPU), the second shared object's ABI (the checks of
-tests/test_abi_cpu.py), and the unchanged default of process_pointcloud."""
+the same fixture (stream consumption and the K logic, without a GPU), and the unchanged default of process_pointcloud."""
 import os
 import random
 
@@ -10,7 +9,6 @@ import pytest
 import torch
 
 import pointprep_ref as ref
-import test_abi_cpu as abi
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
@@ -102,23 +100,6 @@ def test_fixture_cloud_has_no_point_at_the_outlier_threshold(fx):
     data = fx["filtered"]
     _, avg, thr = ref.statistical_outlier(data)
     assert np.count_nonzero(np.abs(avg - thr) <= 1e-4 * thr) <= 1
-
-
-# ---- the second shared object (the checks: tests/test_abi_cpu.py) ---------------------------------------------------------------
-def test_prep_library_exports_declared_abi():
-    abi.check_exports_declared_abi(abi.PREP)
-
-
-def test_prep_ctypes_signatures_match_header_prototypes():
-    abi.check_ctypes_signatures_match_header_prototypes(abi.PREP)
-
-
-def test_prep_c_abi_from_plain_c(tmp_path):
-    abi.check_c_abi_from_plain_c(abi.PREP, tmp_path)
-
-
-def test_prep_library_is_loaded_on_first_use_only():
-    abi.check_loaded_on_first_use_only(abi.PREP)
 
 
 def test_pointprep_has_no_cpu_fallback(fx):

@@ -1,5 +1,4 @@
-"""CPU tests of training on a preprocessed sequence: the sixth shared object's ABI and its loading on first use (the checks of
-tests/test_abi_cpu.py on a row built here) and its argument checks; ``lidar_loss`` on the fp16 train-step fixture
+"""CPU tests of training on a preprocessed sequence: the sixth shared object's argument checks (its C ABI: tests/test_abi_cpu.py); ``lidar_loss`` on the fp16 train-step fixture
 (tests/golden/train_step_losses_f16.npz: the reference's own train_step on half ground truth) and, again, on the fp32 one;
 ``process_pointcloud`` on a fp16 split against the reference's clouds; ``KITTI360Dataset``'s trainer protocol; and the schedule
 of ``Trainer.train``."""
@@ -10,38 +9,15 @@ import torch
 import realdata_cases as rc
 import test_abi_cpu as abi
 
-STEP = abi.Library(binding="_step_lib", header="lidar4d_step.h", prefix="l4ds_", c_file="step_abi_check.c", link="lidar4d_step",
-                   abi=1, names={"l4ds_ray_batch", "l4ds_primary_losses_workspace", "l4ds_primary_losses"}, stream_last=True,
-                   first_use="import lidar4d_amd, lidar4d_amd.trainer, lidar4d_amd.kitti360, lidar4d_amd.ops\n"
-                             "from lidar4d_amd import _step_lib as binding\n"
-                             "assert callable(lidar4d_amd.ops.primary_losses_any) and callable(lidar4d_amd.ops.ray_batch_patches)\n")
 
-
-# ---- the sixth shared object (the checks: tests/test_abi_cpu.py) ----------------------------------------------------------------
-def test_step_library_exports_declared_abi():
-    abi.check_exports_declared_abi(STEP)
-
-
+# Kept under their earlier names, as calls of the checks in tests/test_abi_cpu.py, which run there for every library: a new library
+# adds no test of this kind.
 def test_step_ctypes_signatures_match_header_prototypes():
-    abi.check_ctypes_signatures_match_header_prototypes(STEP)
-
-
-def test_step_c_abi_from_plain_c(tmp_path):
-    abi.check_c_abi_from_plain_c(STEP, tmp_path)
-
-
-def test_step_library_is_loaded_on_first_use_only():
-    abi.check_loaded_on_first_use_only(STEP)
+    abi.test_ctypes_signatures_match_header_prototypes(abi.ROW["step"])
 
 
 def test_step_library_exports_no_name_of_another():
-    import test_patchgrad_cpu
-    mine = abi._exported(abi._binding(STEP).LIB_PATH)
-    assert mine
-    for row in abi.LIBRARIES + [test_patchgrad_cpu.PATCH]:
-        abi._require_built(row, abi._binding(row))
-        theirs = abi._exported(abi._binding(row).LIB_PATH)
-        assert not mine & theirs, (row.link, sorted(mine & theirs)[:8])
+    abi.test_no_library_exports_a_name_of_another()
 
 
 def test_step_argument_checks_need_no_device():
