@@ -29,7 +29,7 @@ extern "C" {
 #endif
 
 #define L4D_MAX_LEVELS 16
-#define L4D_ABI_VERSION 4
+#define L4D_ABI_VERSION 5
 
 /* Multi-resolution hash grid geometry (tiny-cuda-nn "HashGrid" encoding).
  * Filled by host code (lidar4d_amd/gridmeta.py) exactly as tiny-cuda-nn's host code derives it. */
@@ -284,10 +284,15 @@ int l4d_field_width(const l4d_field_desc* f /*host*/);         /* feature column
 int l4d_dyn_pairs_build(const void* const* slice_tables /*host*/, int32_t n_slices, int64_t n_entries, void* pairs, void* stream);
 /* tinfo [8] fp32 (device) <- t: [t, t1=(f+1)/num_frames, t2=(f-1)/num_frames, has_fwd, has_bwd, f] */
 int l4d_time_setup(const float* t, int32_t num_frames, float* tinfo, void* stream);
-/* l4d_sample_rays variant that writes xt [N*T,4] = ((clip(o+d z)+bound)/(2 bound), t) (lidar4d.py:141,148-149) */
+/* l4d_sample_rays variant that writes xt [N*T,4] = ((clip(o+d z)+bound)/(2 bound), t) (lidar4d.py:141,148-149).
+ * live == NULL: every sample of every ray (n_live, s0, S are ignored), z_vals [N,T] and xt [N*T,4] are both written.
+ * live given (ABI 5; the work list of a slab of the culled training march): xt [n_live * S', 4], S' = min(S, T - s0); row
+ * i * S' + (s - s0) holds the bits the dense call writes to row live[i] * T + s for the same noise ([N,T], or null).  z_vals may be
+ * null; given, it is the dense [N,T] array and only the listed samples are written.  Every live[i] must lie in 0 .. N - 1.
+ * T < 1, S < 1, s0 outside 0 .. T - 1 or n_live outside 0 .. N: status 1; n_live == 0 launches nothing. */
 int l4d_sample_rays_xt(const float* rays_o, const float* rays_d, const float* lin, const float* noise,
-                       const float* t, int64_t N, int32_t T, float near, float far, float bound, float* z_vals,
-                       float* xt, void* stream);
+                       const float* t, int64_t N, int32_t T, float near, float far, float bound, const int32_t* live,
+                       int64_t n_live, int32_t s0, int32_t S, float* z_vals, float* xt, void* stream);
 /* flow16 [P,16] fp16: flow network output (cols 0-2 forward, 3-5 backward); X [P,in_pad] fp16.
  * hd_scratch: null, or l4d_density_encode_fwd_workspace() bytes of device scratch -> the xz / yz 2-D x time hash stacks are
  * evaluated by a separate kernel from LDS-resident slice tables (faster from ~1e5 samples), and -- from 2^18 samples on, with

@@ -635,19 +635,30 @@ __global__ void __launch_bounds__(256) sample_rays_xt_kernel(const float* __rest
   if (idx >= N * T) return;
   const int64_t ray = idx / T;
   const int ti = (int)(idx - ray * T);
-  float z = near + (far - near) * lin[ti];
-  if (noise) {
-    const float sample_dist = (far - near) / (float)T;
-    z = z + (noise[idx] - 0.5f) * sample_dist;
-  }
+  const float z = sample_depth(lin, noise ? noise + idx : nullptr, ti, T, near, far);
   z_vals[idx] = z;
-  float4_t o;
-#pragma unroll
-  for (int k = 0; k < 3; ++k) {
-    o[k] = unit_coord(ray_point(rays_o[ray * 3 + k], rays_d[ray * 3 + k], z, bound), bound);
-  }
-  o[3] = *t;
-  *reinterpret_cast<float4_t*>(xt + idx * 4) = o;
+  *reinterpret_cast<float4_t*>(xt + idx * 4) = xt_row(rays_o, rays_d, ray, z, *t, bound);
+}
+
+// ... for a work list: the rows of samples s0 .. s0 + Sp - 1 of the rays live[0 .. n_live), compact and slab-major within the call
+// (row i * Sp + (s - s0) = the dense kernel's row live[i] * T + s, same noise [N, T], same two functions of render_dev.h).  One thread
+// per row: a wavefront stores 1 KiB of consecutive rows as 16-byte words; its reads of live / rays_o / rays_d are wave-broadcasts
+// (Sp >= 64: one ray per wavefront) and of lin / noise 256-byte runs.  z_vals: null, or the dense [N, T] array, of which the listed
+// samples are written.
+__global__ void __launch_bounds__(256) sample_rays_xt_list_kernel(const float* __restrict__ rays_o, const float* __restrict__ rays_d,
+                                                                 const float* __restrict__ lin, const float* __restrict__ noise,
+                                                                 const float* __restrict__ t, const int32_t* __restrict__ live,
+                                                                 int64_t n_live, int T, int s0, int Sp, float near, float far,
+                                                                 float bound, float* __restrict__ z_vals, float* __restrict__ xt) {
+  const int64_t idx = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (idx >= n_live * Sp) return;
+  const int64_t i = idx / Sp;
+  const int ti = s0 + (int)(idx - i * Sp);
+  const int64_t ray = live[i];
+  const int64_t dense = ray * T + ti;
+  const float z = sample_depth(lin, noise ? noise + dense : nullptr, ti, T, near, far);
+  if (z_vals) z_vals[dense] = z;
+  *reinterpret_cast<float4_t*>(xt + idx * 4) = xt_row(rays_o, rays_d, ray, z, *t, bound);
 }
 
 // ================================================================================================
@@ -665,8 +676,21 @@ extern "C" int l4d_time_setup(const float* t, int32_t num_frames, float* tinfo, 
 }
 
 extern "C" int l4d_sample_rays_xt(const float* rays_o, const float* rays_d, const float* lin, const float* noise,
-                                  const float* t, int64_t N, int32_t T, float near, float far, float bound, float* z_vals,
-                                  float* xt, void* stream) {
+                                  const float* t, int64_t N, int32_t T, float near, float far, float bound, const int32_t* live,
+                                  int64_t n_live, int32_t s0, int32_t S, float* z_vals, float* xt, void* stream) {
+  if (live) {  // work-list mode; the checks of l4dr_slab_rows
+    if (T < 1) L4D_FAIL("l4d_sample_rays_xt: T must be at least 1");
+    if (S < 1) L4D_FAIL("l4d_sample_rays_xt: S must be at least 1");
+    if (s0 < 0 || s0 >= T) L4D_FAIL("l4d_sample_rays_xt: s0 outside 0 .. T - 1");
+    if (N < 0 || N > 0x7fffffffll) L4D_FAIL("l4d_sample_rays_xt: N outside 0 .. 2^31 - 1");
+    if (n_live < 0 || n_live > N) L4D_FAIL("l4d_sample_rays_xt: n_live outside 0 .. N");
+    if (n_live == 0) return 0;
+    const int Sp = S < T - s0 ? S : T - s0;
+    L4D_LAUNCH(sample_rays_xt_list_kernel, dim3((unsigned)ceil_div64(n_live * Sp, 256)), dim3(256), 0, (hipStream_t)stream, rays_o,
+               rays_d, lin, noise, t, live, n_live, (int)T, (int)s0, Sp, near, far, bound, z_vals, xt);
+    L4D_LAUNCH_CHECK("l4d_sample_rays_xt");
+    return 0;
+  }
   if (N == 0) return 0;
   L4D_LAUNCH(sample_rays_xt_kernel, dim3((unsigned)ceil_div64(N * T, 256)), dim3(256), 0, (hipStream_t)stream, rays_o,
                      rays_d, lin, noise, t, N, T, near, far, bound, z_vals, xt);

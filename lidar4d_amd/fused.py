@@ -123,6 +123,107 @@ def attribute_stage(model, rays_d, h, weights, idx, count, T, train):
     return image, gathered, XA, actR, actI, attr, attr_c, denc
 
 
+def composite_attribute_bwd(model, T, sample_dist, gathered, tinfo, z_vals, h, sigma, weights, idx, count, XA, actR, actI, attr, attr_c,
+                            denc, d_depth, d_wsum, d_image, d_weights):
+    """The dense front of the render's backward: gradient arena and gates, ``composite_bwd``, the attribute networks on the mask list.
+    -> dh [P, 16] fp16, the adjoint of the density network's output rows (times ``model.loss_scale``), P = N * T dense rows.
+    Shared by ``RenderFn.backward`` and the culled training march (cull.py), whose dense ``h`` is unwritten behind a ray's retirement
+    point: those rows are not in the mask list, and the march never reads their ``dh``."""
+    store = model._store
+    store.prepare_grads()
+    # the current frame's time-slice pair is what receives dynamic-hash gradients (hash_field.py:79-85): raise its
+    # gates for the optimiser (trainer.FlatAdam leaves ungated slices alone, like torch.optim.Adam with grad = None)
+    ops.mark_time_slices(tinfo, model.hash_encoder.hash_dynamic[0].time_resolution, store.gates)
+    ls = float(model.loss_scale)
+    inv = 1.0 / ls
+    P = sigma.numel()
+    dev = sigma.device
+    c = lambda t: None if t is None else t.float().contiguous()
+
+    d_sigma, d_attr = ops.composite_bwd(sigma, z_vals, weights, attr, 2, sample_dist, model.density_scale,
+                                        model.active_sensor, c(d_depth), c(d_wsum), c(d_image), c(d_weights))
+    # attribute networks
+    an = model.intensity_net
+    n_enc = model.view_encoder.n_output_dims
+    sigma_done = False
+    if gathered and XA is None:
+        # rows assembled again; the sigmoid-scatter adjoint in front of each network and the sum + scatter of the two
+        # geo-feature gradients behind them run inside the kernels (first network stores into dh, second adds).  dh starts as
+        # whole rows [density activation's adjoint, 0 x 15] (one dense pass instead of a zero fill + a strided column pass
+        # afterwards); the networks keep that column (accumulate bit 1)
+        dh = torch.empty(P, 16, dtype=torch.float16, device=dev)
+        ops.sigma_bwd_rows(sigma.view(-1), d_sigma.view(-1), ls, dh)
+        sigma_done = True
+        for ch, (net, a_) in enumerate(((model.raydrop_net, actR), (model.intensity_net, actI))):
+            ops.attr_mlp_bwd_gathered(idx, count, P, T, denc, h, model.geo_feat_dim, an.in_pad, a_, None, store.half(net.params),
+                                      an.n_hidden_layers, store.grad_view(net.params), inv, d_attr=d_attr, attr_compact=attr_c,
+                                      channel=ch, loss_scale=ls, dh16=dh, accumulate=(1 if ch == 1 else 0) | 2)
+    else:
+        dh = torch.zeros(P, 16, dtype=torch.float16, device=dev)
+        dyR = torch.empty(P, 16, dtype=torch.float16, device=dev)
+        dyI = torch.empty(P, 16, dtype=torch.float16, device=dev)
+        ops.attr_scatter_bwd(idx, count, P, d_attr, attr_c, ls, dyR, dyI)
+        if gathered:  # rows in the forward's physical column order (three hidden layers)
+            dxaR = ops.attr_mlp_bwd(XA, count, n_enc, model.geo_feat_dim, actR, dyR, store.half(model.raydrop_net.params),
+                                    an.n_hidden_layers, store.grad_view(model.raydrop_net.params), inv)
+            dxaI = ops.attr_mlp_bwd(XA, count, n_enc, model.geo_feat_dim, actI, dyI, store.half(model.intensity_net.params),
+                                    an.n_hidden_layers, store.grad_view(model.intensity_net.params), inv)
+            ops.attr_gather_bwd(idx, count, P, dxaR, dxaI, an.in_pad - 64, n_enc - 64, model.geo_feat_dim, dh, h_layout=True)
+        else:
+            dxaR = ops.mlp_bwd(XA, actR, dyR, store.half(model.raydrop_net.params), an.n_hidden_layers,
+                               store.grad_view(model.raydrop_net.params), inv, n_rows=count, hidden=an.n_neurons)
+            dxaI = ops.mlp_bwd(XA, actI, dyI, store.half(model.intensity_net.params), an.n_hidden_layers,
+                               store.grad_view(model.intensity_net.params), inv, n_rows=count, hidden=an.n_neurons)
+            ops.attr_gather_bwd(idx, count, P, dxaR, dxaI, an.in_pad, n_enc, model.geo_feat_dim, dh)
+    if not sigma_done:
+        ops.sigma_bwd(h, d_sigma.view(-1), ls, dh)
+    return dh
+
+
+def density_flow_bwd(model, t_dev, tinfo, xt, xf, flow16, act_f, X, act_s, dh, samples_per_ray, slice_pair):
+    """The rest of the render's backward, on the rows it is given -- all P = N * T of ``RenderFn``, ray-major (samples_per_ray = T), or
+    the compact rows of the culled training march (cull.py) with their ``dh`` gathered: the density network, the field encode's adjoint,
+    the planes' re-layout, the data-parallel hook, the flow network and its grid, and the reference's ``.grad = None`` for the time slices
+    outside ``slice_pair``.
+    samples_per_ray: what ``ops.density_encode_bwd``'s wave-level band skip may assume (0: nothing)."""
+    store = model._store
+    inv = 1.0 / float(model.loss_scale)
+    dev = xt.device
+    probe = getattr(model, "_bwd_probe", None)  # measurement hook (bench.py: fraction of all-zero adjoint rows); never set in training
+    if probe is not None:
+        probe(dh)
+    # sigma network
+    # (the backward reports max |dX| of the time-plane columns as it stores them: the field adjoint's fixed-point scale)
+    pe = model.planes_encoder
+    n_pl = pe.layout.n_scales * pe.layout.C
+    gd_absmax = torch.zeros(1, dtype=torch.float32, device=dev) if n_pl % 16 == 0 else None  # (rows wider than 128: two launches, each reports the tiles it stores)
+    dX = ops.mlp_bwd(X, act_s, dh, store.half(model.sigma_net.params), model.sigma_net.n_hidden_layers,
+                     store.grad_view(model.sigma_net.params), inv, dx_absmax=gd_absmax, absmax_cols=(n_pl, 2 * n_pl),
+                     hidden=model.sigma_net.n_neurons)
+    # field
+    gcl = torch.zeros(pe.layout.numel, dtype=torch.float32, device=dev)
+    fd = _field_desc(model)
+    vmax = ops.absmax(pe._arena())
+    dflow16 = ops.density_encode_bwd(fd, _field_grads(model, gcl), xt, flow16, tinfo, dX, inv, vmax, samples_per_ray=samples_per_ray,
+                                     gd_absmax=gd_absmax)
+    # channel-last gradient arena -> added onto the planes' [1, C, H, W] gradient views, one launch
+    ops.planes_relayout(pe.layout, [store.grad_view(p).view(p.shape) for p in pe._flat_planes()], gcl, to_channel_last=False,
+                        accumulate=True)
+    # every gradient except the flow field's is final now: a data-parallel trainer starts reducing them here
+    hook = getattr(model, "_grads_ready_hook", None)
+    if hook is not None:
+        hook()
+    # flow network + grid
+    fn = model.flow_net
+    dxf = ops.mlp_bwd(xf, act_f, dflow16, _flow_w16(model), fn.n_hidden, _flow_wgrad(model), inv, hidden=fn.hidden_dim)
+    ops.hashgrid_t_bwd(fn.grid_enc.meta, xt, (0, 1, 2), 1, t_dev, dxf, [store.grad_view(fn.grid_enc.params)], inv)
+    if slice_pair is not None:  # reference semantics for a torch optimiser: untouched slices keep .grad = None (LiDAR4D.run)
+        for hd in model.hash_encoder.hash_dynamic:
+            for s, enc in enumerate(hd.hash_t):
+                if s not in slice_pair:
+                    enc.params.grad = None
+
+
 class RenderFn(torch.autograd.Function):
     # The reference calls render() inside torch.cuda.amp.autocast (runner.py:497).  The node fixes its own precisions
     # (fp16 tables / MFMA operands, fp32 accumulation and compositing), so autocast is switched off inside it and
@@ -180,88 +281,10 @@ class RenderFn(torch.autograd.Function):
     @staticmethod
     @torch.amp.custom_bwd(device_type="cuda")
     def backward(ctx, d_depth, d_image, d_wsum, d_weights, _dz, _di, _dc):
-        model, T, sample_dist = ctx.model, ctx.T, ctx.sample_dist
+        model, T = ctx.model, ctx.T
         (t_dev, tinfo, z_vals, xt, xf, flow16, act_f, X, h, act_s, sigma, weights, idx, count, XA, actR, actI, attr,
          attr_c, denc) = ctx.saved_tensors
-        store = model._store
-        store.prepare_grads()
-        # the current frame's time-slice pair is what receives dynamic-hash gradients (hash_field.py:79-85): raise its
-        # gates for the optimiser (trainer.FlatAdam leaves ungated slices alone, like torch.optim.Adam with grad = None)
-        ops.mark_time_slices(tinfo, model.hash_encoder.hash_dynamic[0].time_resolution, store.gates)
-        ls = float(model.loss_scale)
-        inv = 1.0 / ls
-        P = xt.shape[0]
-        dev = xt.device
-        c = lambda t: None if t is None else t.float().contiguous()
-
-        d_sigma, d_attr = ops.composite_bwd(sigma, z_vals, weights, attr, 2, sample_dist, model.density_scale,
-                                            model.active_sensor, c(d_depth), c(d_wsum), c(d_image), c(d_weights))
-        # attribute networks
-        an = model.intensity_net
-        n_enc = model.view_encoder.n_output_dims
-        sigma_done = False
-        if ctx.gathered and XA is None:
-            # rows assembled again; the sigmoid-scatter adjoint in front of each network and the sum + scatter of the two
-            # geo-feature gradients behind them run inside the kernels (first network stores into dh, second adds).  dh starts as
-            # whole rows [density activation's adjoint, 0 x 15] (one dense pass instead of a zero fill + a strided column pass
-            # afterwards); the networks keep that column (accumulate bit 1)
-            dh = torch.empty(P, 16, dtype=torch.float16, device=dev)
-            ops.sigma_bwd_rows(sigma.view(-1), d_sigma.view(-1), ls, dh)
-            sigma_done = True
-            for ch, (net, a_) in enumerate(((model.raydrop_net, actR), (model.intensity_net, actI))):
-                ops.attr_mlp_bwd_gathered(idx, count, P, T, denc, h, model.geo_feat_dim, an.in_pad, a_, None, store.half(net.params),
-                                          an.n_hidden_layers, store.grad_view(net.params), inv, d_attr=d_attr, attr_compact=attr_c,
-                                          channel=ch, loss_scale=ls, dh16=dh, accumulate=(1 if ch == 1 else 0) | 2)
-        else:
-            dh = torch.zeros(P, 16, dtype=torch.float16, device=dev)
-            dyR = torch.empty(P, 16, dtype=torch.float16, device=dev)
-            dyI = torch.empty(P, 16, dtype=torch.float16, device=dev)
-            ops.attr_scatter_bwd(idx, count, P, d_attr, attr_c, ls, dyR, dyI)
-            if ctx.gathered:  # rows in the forward's physical column order (three hidden layers)
-                dxaR = ops.attr_mlp_bwd(XA, count, n_enc, model.geo_feat_dim, actR, dyR, store.half(model.raydrop_net.params),
-                                        an.n_hidden_layers, store.grad_view(model.raydrop_net.params), inv)
-                dxaI = ops.attr_mlp_bwd(XA, count, n_enc, model.geo_feat_dim, actI, dyI, store.half(model.intensity_net.params),
-                                        an.n_hidden_layers, store.grad_view(model.intensity_net.params), inv)
-                ops.attr_gather_bwd(idx, count, P, dxaR, dxaI, an.in_pad - 64, n_enc - 64, model.geo_feat_dim, dh, h_layout=True)
-            else:
-                dxaR = ops.mlp_bwd(XA, actR, dyR, store.half(model.raydrop_net.params), an.n_hidden_layers,
-                                   store.grad_view(model.raydrop_net.params), inv, n_rows=count, hidden=an.n_neurons)
-                dxaI = ops.mlp_bwd(XA, actI, dyI, store.half(model.intensity_net.params), an.n_hidden_layers,
-                                   store.grad_view(model.intensity_net.params), inv, n_rows=count, hidden=an.n_neurons)
-                ops.attr_gather_bwd(idx, count, P, dxaR, dxaI, an.in_pad, n_enc, model.geo_feat_dim, dh)
-        if not sigma_done:
-            ops.sigma_bwd(h, d_sigma.view(-1), ls, dh)
-        probe = getattr(model, "_bwd_probe", None)  # measurement hook (bench.py: fraction of all-zero adjoint rows); never set in training
-        if probe is not None:
-            probe(dh)
-        # sigma network
-        # (the backward reports max |dX| of the time-plane columns as it stores them: the field adjoint's fixed-point scale)
-        pe = model.planes_encoder
-        n_pl = pe.layout.n_scales * pe.layout.C
-        gd_absmax = torch.zeros(1, dtype=torch.float32, device=dev) if n_pl % 16 == 0 else None  # (rows wider than 128: two launches, each reports the tiles it stores)
-        dX = ops.mlp_bwd(X, act_s, dh, store.half(model.sigma_net.params), model.sigma_net.n_hidden_layers,
-                         store.grad_view(model.sigma_net.params), inv, dx_absmax=gd_absmax, absmax_cols=(n_pl, 2 * n_pl),
-                         hidden=model.sigma_net.n_neurons)
-        # field
-        gcl = torch.zeros(pe.layout.numel, dtype=torch.float32, device=dev)
-        fd = _field_desc(model)
-        vmax = ops.absmax(pe._arena())
-        dflow16 = ops.density_encode_bwd(fd, _field_grads(model, gcl), xt, flow16, tinfo, dX, inv, vmax, samples_per_ray=T, gd_absmax=gd_absmax)
-        # channel-last gradient arena -> added onto the planes' [1, C, H, W] gradient views, one launch
-        ops.planes_relayout(pe.layout, [store.grad_view(p).view(p.shape) for p in pe._flat_planes()], gcl, to_channel_last=False,
-                            accumulate=True)
-        # every gradient except the flow field's is final now: a data-parallel trainer starts reducing them here
-        hook = getattr(model, "_grads_ready_hook", None)
-        if hook is not None:
-            hook()
-        # flow network + grid
-        fn = model.flow_net
-        dxf = ops.mlp_bwd(xf, act_f, dflow16, _flow_w16(model), fn.n_hidden, _flow_wgrad(model), inv, hidden=fn.hidden_dim)
-        ops.hashgrid_t_bwd(fn.grid_enc.meta, xt, (0, 1, 2), 1, t_dev, dxf, [store.grad_view(fn.grid_enc.params)], inv)
-        pair = ctx.slice_pair
-        if pair is not None:  # reference semantics for a torch optimiser: untouched slices keep .grad = None (LiDAR4D.run)
-            for hd in model.hash_encoder.hash_dynamic:
-                for s, enc in enumerate(hd.hash_t):
-                    if s not in pair:
-                        enc.params.grad = None
+        dh = composite_attribute_bwd(model, T, ctx.sample_dist, ctx.gathered, tinfo, z_vals, h, sigma, weights, idx, count, XA, actR, actI,
+                                     attr, attr_c, denc, d_depth, d_wsum, d_image, d_weights)
+        density_flow_bwd(model, t_dev, tinfo, xt, xf, flow16, act_f, X, act_s, dh, T, ctx.slice_pair)
         return (None,) * 7 + (None,) * (len(ctx.needs_input_grad) - 7)

@@ -130,15 +130,24 @@ class LiDAR4D(LiDAR_Renderer):
             super().zero_grad(set_to_none=set_to_none)
 
     # -- fused path ------------------------------------------------------------------------------------------
-    def run(self, rays_o, rays_d, time, num_steps=768, perturb=False, noise=None, time_host=None, early_stop=None, slab=96, **kwargs):
+    def run(self, rays_o, rays_d, time, num_steps=768, perturb=False, noise=None, time_host=None, early_stop=None, slab=96, cull=None,
+            **kwargs):
         """renderer.py:44-140.  ``noise`` ([N, num_steps] in [0,1)) replaces the internal torch.rand when given
         (parity tests feed the oracle's noise).  ``time_host``: the value of ``time`` as a python float when the caller
         has it (the training loop does): spares the one device read-back of a training step -- the host-side copy of
         hash_field.py:79-85's slice choice below, which would otherwise wait for the whole previous step to drain.
         ``early_stop`` (a float >= 0; default None: this path, untouched) with ``slab``: a no-grad render that walks the samples
         front to back in slabs and retires a ray once its transmittance is below ``early_stop`` (early_stop.py: the bound, and the
-        one 4-byte read-back per slab); the result gains ``evaluated_samples`` and ``retired_at``."""
-        if early_stop is not None:
+        one 4-byte read-back per slab); the result gains ``evaluated_samples`` and ``retired_at``.
+        ``cull`` (a float >= 0; default None) with ``slab``: the same march inside a TRAINING render -- grad mode on, field parameters
+        requiring grad, ``perturb`` and ``noise`` as on this path -- whose backward runs on the evaluated samples only (cull.py: the
+        semantics and what the gradient drops); the same two extra keys."""
+        culled = None
+        if cull is not None:
+            from . import cull as cull_mod
+            train = torch.is_grad_enabled() and hasattr(self, "_store") and any(p.requires_grad for _, p, _, n, _ in self._store.entries if n > 0)
+            culled = cull_mod.check_options(self, cull, slab, early_stop, train)
+        elif early_stop is not None:
             return self._run_early_stop(rays_o, rays_d, time, num_steps, perturb, early_stop, slab)
         if not self.fused:  # four or sixteen channels per plane: sampling, density(), compositing, attribute() one after the other
             return LiDAR_Renderer.run(self, rays_o, rays_d, time, num_steps=num_steps, perturb=perturb, noise=noise)
@@ -163,8 +172,15 @@ class LiDAR4D(LiDAR_Renderer):
             t_host = time_host if time_host is not None else (float(time.reshape(-1)[0]) if torch.is_tensor(time) else float(time))
             idx = np.float32(t_host) * np.float32(n_slices - 1)
             self._host_slice_pair = (int(np.floor(idx)), int(np.ceil(idx)))
-        depth, image, wsum, weights, z_vals, idx, count = RenderFn.apply(self, rays_o, rays_d, t_dev, noise, num_steps,
-                                                                        train, *params)
+        extra = {}
+        if culled is not None:
+            depth, image, wsum, weights, z_vals, idx, count, evaluated, retired_at = cull_mod.run(
+                self, rays_o, rays_d, t_dev, noise, num_steps, culled[0], culled[1], params)
+            extra = {"evaluated_samples": evaluated,  # density rows actually computed (device int64 scalar), of N * num_steps
+                     "retired_at": retired_at}        # [N] int32: samples evaluated per ray
+        else:
+            depth, image, wsum, weights, z_vals, idx, count = RenderFn.apply(self, rays_o, rays_d, t_dev, noise, num_steps,
+                                                                            train, *params)
         return {
             "depth_lidar": depth.view(*prefix),
             "image_lidar": image.view(*prefix, self.out_lidar_dim),
@@ -173,6 +189,7 @@ class LiDAR4D(LiDAR_Renderer):
             "z_vals": z_vals,
             "mask_idx": idx,      # extra: compacted `weights > 1e-4` sample indices (renderer.py:110) ...
             "mask_count": count,  # ... and their number (device int32), the attribute work list
+            **extra,
         }
 
     def _run_early_stop(self, rays_o, rays_d, time, num_steps, perturb, early_stop, slab):

@@ -315,14 +315,33 @@ def sample_rays(rays_o, rays_d, lin, noise, near, far, bound, want_xyz=True):
     return z, xyz
 
 
-def sample_rays_xt(rays_o, rays_d, lin, noise, t_dev, near, far, bound):
+def sample_rays_xt(rays_o, rays_d, lin, noise, t_dev, near, far, bound, live=None, n_live=None, s0=0, S=None, out=None):
+    """-> z_vals [N, T], xt [N * T, 4].  With a work list ``live`` (int32, its first ``n_live`` entries; default all of it): -> xt
+    [n_live * S', 4] alone, S' = min(S, T - s0), whose row i * S' + (s - s0) holds the bits the dense call writes to row
+    live[i] * T + s for the same noise.  out: the rows' destination (a contiguous fp32 [>= rows, 4] view), else allocated."""
     _chk(rays_o, torch.float32, "rays_o"), _chk(rays_d, torch.float32, "rays_d"), _chk(lin, torch.float32, "lin")
     _chk(noise, torch.float32, "noise"), _chk(t_dev, torch.float32, "t")
     N, T = rays_o.shape[0], lin.shape[0]
+    if noise is not None and noise.numel() != N * T:
+        raise ValueError("sample_rays_xt: noise must be [N, T]")
+    if live is not None:
+        _chk(live, torch.int32, "live"), _chk(out, torch.float32, "out")
+        n_live = live.numel() if n_live is None else int(n_live)
+        S = T if S is None else S
+        if n_live > live.numel():
+            raise ValueError("sample_rays_xt: n_live exceeds the live list")
+        rows = n_live * max(0, min(S, T - s0))
+        if out is None:
+            out = torch.empty(rows, 4, dtype=torch.float32, device=rays_o.device)
+        elif out.numel() < rows * 4:
+            raise ValueError("sample_rays_xt: out is smaller than the work list's rows")
+        call("l4d_sample_rays_xt", _p(rays_o), _p(rays_d), _p(lin), _p(noise), _p(t_dev), N, T, float(near), float(far),
+             float(bound), _p(live), n_live, int(s0), int(S), None, _p(out), _stream())
+        return out[:rows]
     z = torch.empty(N, T, dtype=torch.float32, device=rays_o.device)
     xt = torch.empty(N * T, 4, dtype=torch.float32, device=rays_o.device)
     call("l4d_sample_rays_xt", _p(rays_o), _p(rays_d), _p(lin), _p(noise), _p(t_dev), N, T, float(near), float(far),
-         float(bound), _p(z), _p(xt), _stream())
+         float(bound), None, 0, 0, 0, _p(z), _p(xt), _stream())
     return z, xt
 
 
@@ -392,17 +411,22 @@ def attr_mlp_fwd(idx, count, cap, T, dir_enc16, h16, n_geo, in_pad, weights16, n
     return y, act
 
 
-def mlp_fwd_sigma(x16, weights16, n_hidden, save_act=True, hidden=64):
-    """mlp_fwd + the density activation as epilogue -> (y [P,16] fp16, act, sigma [P] fp32 = exp(y[:, 0]))."""
+def mlp_fwd_sigma(x16, weights16, n_hidden, save_act=True, hidden=64, y=None, sigma=None):
+    """mlp_fwd + the density activation as epilogue -> (y [P,16] fp16, act, sigma [P] fp32 = exp(y[:, 0])).
+    y / sigma: the outputs' destinations (contiguous views of P rows), else allocated."""
     _chk(x16, torch.float16, "x"), _chk(weights16, torch.float16, "weights")
+    _chk(y, torch.float16, "y"), _chk(sigma, torch.float32, "sigma")
     P, in_pad = x16.shape
-    if hidden != 64:
+    if (y is not None and y.numel() != P * 16) or (sigma is not None and sigma.numel() != P):
+        raise ValueError("mlp_fwd_sigma: y / sigma must hold exactly the rows of x")
+    if sigma is None:
         sigma = torch.empty(P, dtype=torch.float32, device=x16.device)
-        y, act = mlp_fwd(x16, weights16, n_hidden, save_act=save_act, hidden=hidden, sigma=sigma)
+    if hidden != 64:
+        y, act = mlp_fwd(x16, weights16, n_hidden, save_act=save_act, hidden=hidden, sigma=sigma, y=y)
         return y, act, sigma
-    y = torch.empty(P, 16, dtype=torch.float16, device=x16.device)
+    if y is None:
+        y = torch.empty(P, 16, dtype=torch.float16, device=x16.device)
     act = torch.empty(n_hidden, P, 64, dtype=torch.float16, device=x16.device) if save_act else None
-    sigma = torch.empty(P, dtype=torch.float32, device=x16.device)
     call("l4d_mlp_fwd_sigma", _p(x16), P, in_pad, n_hidden, _p(weights16), _p(y), _p(act), _p(sigma), _stream())
     return y, act, sigma
 
@@ -487,15 +511,21 @@ def time_setup(t_dev, num_frames, tinfo=None):
     return tinfo
 
 
-def density_encode_fwd(field_desc, xt, flow16, tinfo, in_pad, X=None, sigma_weights16=None, n_hidden=0, save_act=True, rows_like_points=None):
+def density_encode_fwd(field_desc, xt, flow16, tinfo, in_pad, X=None, sigma_weights16=None, n_hidden=0, save_act=True, rows_like_points=None,
+                       y=None, sigma=None):
     """-> X [P, in_pad] fp16.  With ``sigma_weights16`` (the density network's fp16 weights): -> (X, y [P,16] fp16, act or None,
     sigma [P] fp32) = the rows AND ``mlp_fwd_sigma`` of them in one call (l4d_density_encode_sigma_fwd: for the default network
     shape the network runs inside the encode kernel).
     rows_like_points: take the time planes' form (1-D rows and two taps, or four taps) a batch of that many points would take
     instead of P's: the two round differently (one fp16 unit in a few plane columns), and the slabs of an early-terminating
-    march (early_stop.py) are pieces of one batch."""
+    march (early_stop.py) are pieces of one batch.
+    X / y / sigma: the outputs' destinations (contiguous views of exactly P rows), else allocated."""
     _chk(xt, torch.float32, "xt"), _chk(flow16, torch.float16, "flow16"), _chk(tinfo, torch.float32, "tinfo")
+    _chk(X, torch.float16, "X"), _chk(y, torch.float16, "y"), _chk(sigma, torch.float32, "sigma")
     P = xt.shape[0]
+    if ((X is not None and X.numel() != P * in_pad) or (y is not None and y.numel() != P * 16)
+            or (sigma is not None and sigma.numel() != P)):
+        raise ValueError("density_encode_fwd: X / y / sigma must hold exactly the rows of xt")
     if X is None:
         X = torch.empty(P, in_pad, dtype=torch.float16, device=xt.device)
     scratch = None
@@ -507,9 +537,11 @@ def density_encode_fwd(field_desc, xt, flow16, tinfo, in_pad, X=None, sigma_weig
         rows = torch.empty(_lib.lib().l4d_plane_rows_workspace(C.byref(field_desc)) // 4, dtype=torch.float32, device=xt.device)
     if sigma_weights16 is not None:
         _chk(sigma_weights16, torch.float16, "sigma weights")
-        y = torch.empty(P, 16, dtype=torch.float16, device=xt.device)
+        if y is None:
+            y = torch.empty(P, 16, dtype=torch.float16, device=xt.device)
         act = torch.empty(n_hidden, P, 64, dtype=torch.float16, device=xt.device) if save_act else None
-        sigma = torch.empty(P, dtype=torch.float32, device=xt.device)
+        if sigma is None:
+            sigma = torch.empty(P, dtype=torch.float32, device=xt.device)
         call("l4d_density_encode_sigma_fwd", C.byref(field_desc), _p(xt), _p(flow16), _p(tinfo), P, _p(X), in_pad, _p(scratch), _p(rows),
              _p(sigma_weights16), int(n_hidden), _p(y), _p(act), _p(sigma), _stream())
         return X, y, act, sigma

@@ -85,6 +85,8 @@ class LiDAR_Renderer(nn.Module):
         """Generic (un-fused) run for subclasses that only define density()/attribute()."""
         if kwargs.get("early_stop") is not None:
             raise ValueError("early_stop needs the fused pipeline (LiDAR4D with model.fused): this run evaluates every sample")
+        if kwargs.get("cull") is not None:
+            raise ValueError("cull needs the fused pipeline (LiDAR4D with model.fused): this run evaluates every sample")
         prefix = rays_o.shape[:-1]
         rays_o = rays_o.contiguous().view(-1, 3).float()
         rays_d = rays_d.contiguous().view(-1, 3).float()
@@ -146,6 +148,9 @@ class LiDAR_Renderer(nn.Module):
 
     def render(self, rays_o, rays_d, time, staged=False, max_ray_batch=4096, **kwargs):
         _run = self.run
+        if staged and kwargs.get("cull") is not None:  # (the option's other refusals: cull.check_options, from run)
+            raise ValueError("cull is a training option and staged=True renders a frame in chunks without a gradient: not supported "
+                             "together (for inference use early_stop)")
         B, N = rays_o.shape[:2]
         device = rays_o.device
         if staged:

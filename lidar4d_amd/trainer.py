@@ -881,6 +881,12 @@ def _march_kw(early_stop, slab):
     return {} if early_stop is None else {"early_stop": early_stop, "slab": slab}
 
 
+def _cull_kw(trainer):
+    """The render keywords of a culled training step; none at all when ``cull`` is not set (the plain render's call)."""
+    cull = getattr(trainer, "cull", None)
+    return {} if cull is None else {"cull": cull, "slab": getattr(trainer, "cull_slab", 128)}
+
+
 class Trainer:
     """One process per GPU.  Rays (whole frames) are sharded across ranks -- each rank draws its own frame and ray
     indices -- parameters are replicated and the flat gradient buffer is SUM-all-reduced once per step (the primary
@@ -892,7 +898,7 @@ class Trainer:
                  grad_transport="fp32", graph_batch_inside=True, flow_loss_stream=True, point_removal=None,
                  depth_grad_loss="l1", sobel_grad=False, grad_loss=True, grad_norm_smooth=False, spatial_smooth=False,
                  tv_loss=False, alpha_grad=0.1, alpha_grad_norm=0.1, alpha_spatial=0.1, alpha_tv=0.1, fused_patch=None,
-                 change_patch_size_lidar=None, change_patch_size_epoch=2, pointcloud_dataset=None):
+                 change_patch_size_lidar=None, change_patch_size_epoch=2, pointcloud_dataset=None, cull=None, cull_slab=128):
         """Defaults follow the reference's default run: the ray chamfer term is always part of its step
         (runner.py:215-220) and ``--flow_loss`` defaults to True (main_lidar4d.py:67).
         chamfer: a mean over the rank's own rays, so under data parallelism it is scaled by 1/world before the SUM
@@ -910,7 +916,11 @@ class Trainer:
         dataset before the batch of every step of an epoch with ``epoch % change_patch_size_epoch == 0`` (epochs count from 1),
         and 1 in the other epochs.
         pointcloud_dataset: the split the scene-flow clouds are built from -- the reference hands ``train()`` its ``refine``
-        loader for that (runner.py:691-692: the training frames, served whole); default: ``dataset``."""
+        loader for that (runner.py:691-692: the training frames, served whole); default: ``dataset``.
+        cull / cull_slab: train on culled samples -- every step's render is ``model.render(..., cull=cull, slab=cull_slab)``, which
+        retires a ray once its transmittance is below ``cull`` (tested every ``cull_slab`` samples) and runs the backward on the
+        evaluated samples only (lidar4d_amd/cull.py: the semantics, and what the gradient drops).  The march needs the host between
+        slabs, so steps run eagerly (``graphs_supported()`` is False).  None (default): every sample, as before."""
         self.model, self.dataset, self.num_steps, self.chamfer = model, dataset, num_steps, chamfer
         self.flow, self.urf, self.iters = flow, urf, iters
         self.loss_kinds = dict(depth_loss=depth_loss, raydrop_loss=raydrop_loss, intensity_loss=intensity_loss)
@@ -935,6 +945,7 @@ class Trainer:
                 raise ValueError(f"Trainer: num_rays = {rays} is not a whole number of {px} x {py} patches (change_patch_size_lidar)")
             if self.change_patch_size_epoch < 1:
                 raise ValueError("Trainer: change_patch_size_epoch must be at least 1")
+        self.cull, self.cull_slab = cull, cull_slab
         self.graph_batch_inside = bool(graph_batch_inside)
         # flow_loss_stream: the scene-flow term (about 50 small launches on a frame's point clouds, none of which fills the chip) runs
         # on a stream of its own next to the render path's forward and backward (eager steps only; a captured step keeps one stream)
@@ -1026,8 +1037,11 @@ class Trainer:
         patch terms and the line-of-sight term only as their fused nodes (``fused_patch``; ``fused_urf``: its tolerance follows
         the optimiser's schedule on the device, the torch restatement ``urf_loss`` computes it on the host from
         ``opt.step_count``).  A ``KITTI360Dataset`` draws on the device when it is preloaded there (``device_batches``).
-        A model without the fused pipeline (``model.fused`` False) is never captured."""
+        A model without the fused pipeline (``model.fused`` False) is never captured, nor is a step that trains on culled samples
+        (``cull``)."""
         if not getattr(self.model, "fused", True):  # four or sixteen channels per plane: density() reads the time on the host
+            return False
+        if getattr(self, "cull", None) is not None:  # the culled march reads the live count on the host after every slab (cull.py)
             return False
         patches = getattr(self.dataset, "patch_size_lidar", 1) != 1 or getattr(self, "change_patch_size_lidar", None) is not None
         return (self.reducer is None and (not self.urf or getattr(self, "fused_urf", False)) and hasattr(self.dataset, "batch_for") and hasattr(self.dataset, "next_frame")
@@ -1110,7 +1124,7 @@ class Trainer:
                 with torch.cuda.stream(side):
                     flow_term = self._flow_term(data, t_ground)
             out = self.model.render(data["rays_o_lidar"], data["rays_d_lidar"], data["time"], staged=False, perturb=True,
-                                    num_steps=self.num_steps, time_host=data.get("time_host"))
+                                    num_steps=self.num_steps, time_host=data.get("time_host"), **_cull_kw(self))
             if side is not None:
                 torch.cuda.current_stream().wait_stream(side)
                 flow_term.record_stream(torch.cuda.current_stream())
