@@ -43,7 +43,11 @@ def pano_to_lidar(pano, lidar_K):
 
 
 def lidar_to_pano_with_intensities(local_points_with_intensities, lidar_H, lidar_W, lidar_K, max_depth=80):
-    """convert.py:4-66: [N,4] points in the sensor frame -> (pano [H,W], intensities [H,W])."""
+    """convert.py:4-66: [N,4] points in the sensor frame -> (pano [H,W], intensities [H,W]).
+
+    One difference from the reference: a point at the origin (range 0, as raw scans hold for missing returns) writes nothing
+    here, so a pixel without a return is 0 in both images.  The reference's loop treats a range of 0 as "pixel not set": such a
+    point projects to row H * fov_up / fov, column W / 2 and leaves its INTENSITY there while the range stays 0."""
     pts = _f32(local_points_with_intensities, "local_points_with_intensities")
     if pts.dim() != 2 or pts.shape[1] != 4:
         raise ValueError("lidar_to_pano_with_intensities: expected [N, 4] points")
