@@ -29,7 +29,7 @@ extern "C" {
 #endif
 
 #define L4D_MAX_LEVELS 16
-#define L4D_ABI_VERSION 5
+#define L4D_ABI_VERSION 6
 
 /* Multi-resolution hash grid geometry (tiny-cuda-nn "HashGrid" encoding).
  * Filled by host code (lidar4d_amd/gridmeta.py) exactly as tiny-cuda-nn's host code derives it. */
@@ -172,9 +172,16 @@ int l4d_mlp_bwd(const void* x, const void* act, const void* dy, int64_t P, const
 /* ---- LiDAR_Renderer.run : model/renderer.py:59-129 -----------------------------------------------
  * sample: lin [T] = torch.linspace(0,1,T) (renderer.py:77; passed in so that the bits are the caller's
  * torch build's), noise [N,T] in [0,1) or null (renderer.py:84) -> z_vals [N,T]; xyz [N*T,3] clipped to
- * [-bound,bound] (renderer.py:88-89) or null */
+ * [-bound,bound] (renderer.py:88-89) or null.
+ * ABI 6, occupancy flags as a by-product: occ null = the call as before (occ_res, slab, slab_flags ignored).  With occ, a bit grid
+ * of occ_res^3 cells in ceil(occ_res^3 / 32) uint32 words -- cell (cx, cy, cz) is bit i & 31 of word i >> 5, i = (cz R + cy) R + cx
+ * -- a second kernel writes slab_flags [N, ceil(T / slab)] uint8 with plain stores: entry (r, k) is 1 iff some sample s in
+ * k slab .. min(T, (k + 1) slab) - 1 of ray r lies in a set cell, the cell of a sample being c_d = min(R - 1, max(0,
+ * (int)floorf(u_d R))) with u_d = (p_d + bound) / (2 bound) of the clipped position p written to xyz: the fp32 expression of
+ * l4d_sample_rays_xt's rows.  z_vals and xyz as before.  occ_res < 1, slab < 1 or a null slab_flags: status 1. */
 int l4d_sample_rays(const float* rays_o, const float* rays_d, const float* lin, const float* noise, int64_t N,
-                    int32_t T, float near, float far, float bound, float* z_vals, float* xyz, void* stream);
+                    int32_t T, float near, float far, float bound, float* z_vals, float* xyz, const uint32_t* occ,
+                    int32_t occ_res, int32_t slab, uint8_t* slab_flags, void* stream);
 /* composite: sigma [N,T] -> weights [N,T], weights_sum [N], depth [N] (= sum w z, not normalised),
  * mask [N,T] (uint8, weights > 1e-4, renderer.py:110) and the compacted list of masked flat sample
  * indices (grouped by ray, ascending inside a ray) + its length (device int32, zeroed here). */

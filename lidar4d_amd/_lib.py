@@ -12,7 +12,7 @@ LIB_PATH = os.environ.get("L4D_LIB", os.path.join(_HERE, "liblidar4d_hip.so"))  
 L4D_MAX_LEVELS = 16
 L4D_MAX_TIME_SLICES = 8
 L4D_MAX_PLANE_SCALES = 8
-ABI_VERSION = 5
+ABI_VERSION = 6
 
 # The binding modules of the package, one per shared library, in load order: this one (mapped with the package), then those mapped on
 # first use.  Names only -- importing them here would import every library's host side with the package.
@@ -79,7 +79,7 @@ SIGNATURES = {
     "l4d_freq_fwd": [P, I64, I32, I32, P, I32, P],
     "l4d_mlp_fwd": [P, I64, P, I32, I32, P, P, P, P],
     "l4d_mlp_bwd": [P, P, P, I64, P, I32, I32, P, P, P, F32, P, I32, I32, P],
-    "l4d_sample_rays": [P, P, P, P, I64, I32, F32, F32, F32, P, P, P],
+    "l4d_sample_rays": [P, P, P, P, I64, I32, F32, F32, F32, P, P, P, I32, I32, P, P],
     "l4d_sample_rays_xt": [P, P, P, P, P, I64, I32, F32, F32, F32, P, I64, I32, I32, P, P, P],
     "l4d_composite_fwd": [P, P, I64, I32, F32, F32, I32, P, P, P, P, P, P, P],
     "l4d_composite_image": [P, P, I64, I32, I32, P, P],

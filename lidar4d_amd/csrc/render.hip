@@ -64,6 +64,49 @@ __global__ void __launch_bounds__(256) sample_rays_kernel(const float* __restric
   }
 }
 
+// ---- occupancy flags of a ray's slabs (l4d_sample_rays with a grid) -------------------------------
+// flags[ray, k] = 1 iff a sample of slab k of the ray -- samples k * slab .. min(T, (k + 1) * slab) - 1 -- lies in a set cell of the
+// R^3 bit grid occ (cell (cx, cy, cz): bit i & 31 of word i >> 5, i = (cz R + cy) R + cx).  One wavefront per ray: lane l tests the
+// slab's samples l, l + 64, ... (sample_rays_kernel's depth, sample_rays_xt_kernel's unit coordinates: shared device functions, so
+// the cell is the one the field kernels' row falls into), one ballot per slab, lane 0 stores the byte.  No atomics, no LDS, no
+// barrier: a wavefront behind the last ray leaves at once.  The cell index is clamped to 0 .. R - 1 whatever the position is
+// (a NaN converts to 0), so every read of occ is inside its ceil(R^3 / 32) words.
+#define SF_RAYS 4  // rays (wavefronts) per workgroup of slab_flags_kernel
+__global__ void __launch_bounds__(64 * SF_RAYS) slab_flags_kernel(const float* __restrict__ rays_o, const float* __restrict__ rays_d,
+                                                                   const float* __restrict__ lin, const float* __restrict__ noise,
+                                                                   int64_t N, int T, float near, float far, float bound,
+                                                                   const uint32_t* __restrict__ occ, int R, int slab, int n_slabs,
+                                                                   uint8_t* __restrict__ flags) {
+  const int lane = threadIdx.x & 63;
+  const int64_t ray = (int64_t)blockIdx.x * SF_RAYS + (threadIdx.x >> 6);
+  if (ray >= N) return;  // wave-uniform
+  float o[3], d[3];
+#pragma unroll
+  for (int k = 0; k < 3; ++k) {
+    o[k] = rays_o[ray * 3 + k];
+    d[k] = rays_d[ray * 3 + k];
+  }
+  const float Rf = (float)R;
+  for (int k = 0; k < n_slabs; ++k) {
+    const int begin = k * slab;                  // (k < n_slabs = ceil(T / slab): begin < T)
+    const int end = begin + min(slab, T - begin);
+    bool hit = false;
+    for (int64_t s = begin + lane; s < end && !hit; s += 64) {
+      const float z = sample_depth(lin, noise ? noise + ray * T + s : nullptr, (int)s, T, near, far);
+      int64_t cell = 0;
+#pragma unroll
+      for (int a = 2; a >= 0; --a) {
+        const float u = unit_coord(ray_point(o[a], d[a], z, bound), bound);
+        const int c = min(R - 1, max(0, (int)floorf(u * Rf)));
+        cell = cell * R + c;
+      }
+      hit = (occ[cell >> 5] >> (uint32_t)(cell & 31)) & 1u;
+    }
+    const unsigned long long any = __ballot(hit);  // (every lane of the wavefront is here: the loop above has no early exit past it)
+    if (lane == 0) flags[ray * n_slabs + k] = any ? 1 : 0;
+  }
+}
+
 // ---- compositing forward (renderer.py:98-110,121-126) ------------------------------------------
 #define CF_RAYS 16  // rays (wavefronts) per workgroup of composite_fwd_kernel
 __global__ void __launch_bounds__(64 * CF_RAYS) composite_fwd_kernel(const float* __restrict__ sigma, const float* __restrict__ z_vals,
@@ -525,11 +568,25 @@ extern "C" int l4d_sigma_bwd_rows(const float* sigma, const float* d_sigma, int6
 }
 
 extern "C" int l4d_sample_rays(const float* rays_o, const float* rays_d, const float* lin, const float* noise, int64_t N,
-                               int32_t T, float near, float far, float bound, float* z_vals, float* xyz, void* stream) {
+                               int32_t T, float near, float far, float bound, float* z_vals, float* xyz, const uint32_t* occ,
+                               int32_t occ_res, int32_t slab, uint8_t* slab_flags, void* stream) {
+  if (occ) {
+    if (occ_res < 1) L4D_FAIL("l4d_sample_rays: occ_res must be at least 1");
+    if (slab < 1) L4D_FAIL("l4d_sample_rays: slab must be at least 1");
+    if (!slab_flags) L4D_FAIL("l4d_sample_rays: occ given without slab_flags");
+    if (T < 1) L4D_FAIL("l4d_sample_rays: T must be at least 1");
+    if (N < 0 || N > 0x7fffffffll) L4D_FAIL("l4d_sample_rays: N outside 0 .. 2^31 - 1");
+  }
   if (N == 0) return 0;
   L4D_LAUNCH(sample_rays_kernel, dim3((unsigned)ceil_div64(N * T, 256)), dim3(256), 0, (hipStream_t)stream, rays_o,
                      rays_d, lin, noise, N, T, near, far, bound, z_vals, xyz);
   L4D_LAUNCH_CHECK("l4d_sample_rays");
+  if (occ) {
+    const int n_slabs = (int)ceil_div64(T, slab);
+    L4D_LAUNCH(slab_flags_kernel, dim3((unsigned)ceil_div64(N, SF_RAYS)), dim3(64 * SF_RAYS), 0, (hipStream_t)stream, rays_o, rays_d,
+               lin, noise, N, T, near, far, bound, occ, occ_res, slab, n_slabs, slab_flags);
+    L4D_LAUNCH_CHECK("l4d_sample_rays");
+  }
   return 0;
 }
 

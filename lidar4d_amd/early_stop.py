@@ -18,6 +18,11 @@ a slab's rows as on the whole batch -- see the comment in ``run`` -- and the enc
 (include/lidar4d_march.h: l4dr_slab_rows in front, l4dr_slab_update behind), and the HOST READS ONE int32, the number of live
 rays, to size the next slab's launches: a deliberate exception to "no host synchronisation", for inference only.  Nothing else is
 read back, and a march is never captured into a graph.
+
+With ``occupancy=grid`` (occupancy.py) the march also skips empty space in FRONT of the surface: a slab of a ray is evaluated only
+where the ray is alive and one of the slab's samples lies in a set cell of the grid (``run_skipping``).  The result is then the full
+render with sigma set to 0 at every sample of a skipped (ray, slab) and behind each ray's retirement point; what that costs in
+accuracy depends on the grid and is what ``OccupancyGrid.audit`` measures.
 """
 import math
 
@@ -99,9 +104,12 @@ def slab_update(sigma_c, h_c, z_vals, live, n_live, s0, S, sample_dist, density_
 
 
 # ---- the march -----------------------------------------------------------------------------------------------------------------
-def run(model, rays_o, rays_d, t_dev, num_steps, eps, S):
+def run(model, rays_o, rays_d, t_dev, num_steps, eps, S, occupancy=None):
     """``RenderFn.forward`` with the density stage walked slab by slab.  rays_o / rays_d [N, 3] fp32, t_dev one fp32 on the device.
-    -> depth, image, wsum, weights, z_vals, idx, count (as RenderFn), evaluated_samples (int64 scalar), retired_at [N] int32."""
+    -> depth, image, wsum, weights, z_vals, idx, count (as RenderFn), evaluated_samples (int64 scalar), retired_at [N] int32.
+    occupancy: an ``occupancy.OccupancyGrid`` -- the march of ``run_skipping`` below; None: this function as it always was."""
+    if occupancy is not None:
+        return run_skipping(model, rays_o, rays_d, t_dev, num_steps, eps, S, occupancy)
     store = model._store
     N, T = rays_o.shape[0], int(num_steps)
     dev = rays_o.device
@@ -141,6 +149,62 @@ def run(model, rays_o, rays_d, t_dev, num_steps, eps, S):
             live, live_next = live_next, live
             if s0 < T:
                 n_live = int(n_next.item())  # THE read-back: four bytes per slab, the size of the next slab's launches
+        weights, wsum, depth, _, idx, count = ops.composite_fwd(sigma, z_vals, sample_dist, model.density_scale, model.active_sensor,
+                                                                want_mask=False, want_idx=True)
+        image = attribute_stage(model, rays_d, h, weights, idx, count, T, False)[0]
+        evaluated = torch.tensor(evaluated, dtype=torch.int64, device=dev)
+    return depth, image, wsum, weights, z_vals, idx, count, evaluated, retired_at
+
+
+def run_skipping(model, rays_o, rays_d, t_dev, num_steps, eps, S, grid):
+    """``run`` with an occupancy grid (occupancy.py): a slab of a ray is evaluated only if the ray is alive AND some sample of that
+    slab lies in a set cell of ``grid`` -- the flags ``l4d_sample_rays`` writes beside z_vals, one call up front.  The result is the
+    full render with sigma set to 0 at every sample of a skipped (ray, slab) and behind each ray's retirement point: a skipped slab
+    leaves the ray's transmittance as it is (its factors (1 - 0) + 1e-15f are exactly 1.0f), so ``trans`` stays composite_fwd's prefix
+    product on that sigma.  Same returns as ``run``; ``retired_at`` is each ray's retirement point (T for a ray never retired) and
+    ``evaluated_samples`` counts the rows actually evaluated.  The host reads one int32 per evaluated slab, as in ``run`` -- how many of the
+    slab's rays go on -- and, only behind a slab that retired somebody, the number of rays with work in each slab ahead; a slab that every
+    ray skips costs no read and no launch."""
+    from .occupancy import field_sigma
+    N, T = rays_o.shape[0], int(num_steps)
+    dev = rays_o.device
+    near32, far32 = np.float32(model.near_lidar), np.float32(model.far_lidar)
+    sample_dist = float(np.float32(far32 - near32) / np.float32(T))
+    with torch.no_grad(), torch.autocast(device_type=dev.type, enabled=False):
+        lin = model._lin(T, dev)
+        tinfo = ops.time_setup(t_dev, model.num_frames)
+        z_vals, _, flags = ops.sample_rays(rays_o, rays_d, lin, None, float(near32), float(far32), model.bound, want_xyz=False,
+                                           occ=(grid.bits, grid.R), slab=S)
+        flags = flags.bool().t().contiguous()  # [n_slabs, N]
+        sigma = torch.zeros(N, T, dtype=torch.float32, device=dev)
+        h = torch.empty(N * T, 16, dtype=torch.float16, device=dev)  # (rows of samples never evaluated: sigma 0, weight 0, not listed)
+        retired_at = torch.full((N,), T, dtype=torch.int32, device=dev)
+        trans = torch.ones(N, dtype=torch.float32, device=dev)
+        alive = torch.ones(N, dtype=torch.bool, device=dev)
+        live_next, n_next = torch.empty(N, dtype=torch.int32, device=dev), torch.empty(1, dtype=torch.int32, device=dev)
+        # work[k]: the rays alive now and flagged in slab k, on the host.  alive changes only when a slab retires somebody, so until
+        # then the counts of the slabs ahead are exact: a slab nobody has work in costs nothing, and once no ray is alive the rest of
+        # the walk is host arithmetic.
+        work = flags.sum(1).tolist()
+        s0, k, evaluated = 0, 0, 0
+        while s0 < T:
+            Sp = min(S, T - s0)
+            n_act = work[k]
+            if n_act > 0:
+                active = torch.nonzero_static(alive & flags[k], size=n_act).view(-1).to(torch.int32)  # ascending, as ``run``'s live list
+                xt = slab_rows(rays_o, rays_d, lin, t_dev, active, n_act, s0, S, float(near32), float(far32), model.bound)
+                # (the calls of ``run`` on the compact rows, in the form the whole batch would take)
+                sigma_c, h_c = field_sigma(model, xt, t_dev, tinfo, rows_like_points=N * T)
+                slab_update(sigma_c, h_c, z_vals, active, n_act, s0, S, sample_dist, model.density_scale, model.active_sensor, eps, trans,
+                            sigma, h, retired_at, live_next, n_next)
+                evaluated += n_act * Sp
+                # THE read-back, as in ``run``: how many of the slab's rays go on (eps = 0: nothing is ever retired, nothing is read).
+                # If some do not, alive takes slab_update's own comparison on the same fp32 value and the counts are read again.
+                if eps > 0 and s0 + Sp < T and int(n_next.item()) < n_act:
+                    alive &= ~(trans < eps)
+                    work = (flags & alive).sum(1).tolist()
+            s0 += Sp
+            k += 1
         weights, wsum, depth, _, idx, count = ops.composite_fwd(sigma, z_vals, sample_dist, model.density_scale, model.active_sensor,
                                                                 want_mask=False, want_idx=True)
         image = attribute_stage(model, rays_d, h, weights, idx, count, T, False)[0]

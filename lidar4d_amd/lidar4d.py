@@ -131,7 +131,7 @@ class LiDAR4D(LiDAR_Renderer):
 
     # -- fused path ------------------------------------------------------------------------------------------
     def run(self, rays_o, rays_d, time, num_steps=768, perturb=False, noise=None, time_host=None, early_stop=None, slab=96, cull=None,
-            **kwargs):
+            occupancy=None, **kwargs):
         """renderer.py:44-140.  ``noise`` ([N, num_steps] in [0,1)) replaces the internal torch.rand when given
         (parity tests feed the oracle's noise).  ``time_host``: the value of ``time`` as a python float when the caller
         has it (the training loop does): spares the one device read-back of a training step -- the host-side copy of
@@ -141,14 +141,20 @@ class LiDAR4D(LiDAR_Renderer):
         one 4-byte read-back per slab); the result gains ``evaluated_samples`` and ``retired_at``.
         ``cull`` (a float >= 0; default None) with ``slab``: the same march inside a TRAINING render -- grad mode on, field parameters
         requiring grad, ``perturb`` and ``noise`` as on this path -- whose backward runs on the evaluated samples only (cull.py: the
-        semantics and what the gradient drops); the same two extra keys."""
+        semantics and what the gradient drops); the same two extra keys.
+        ``occupancy`` (an ``occupancy.OccupancyGrid``; default None) with ``early_stop``: the march also skips the slabs of a ray none
+        of whose samples lies in a set cell of the grid (occupancy.py: the semantics and the audit; ``early_stop=0.0`` skips without
+        retiring)."""
+        if occupancy is not None and (early_stop is None or cull is not None):
+            raise ValueError("occupancy needs early_stop (the no-grad march; early_stop=0.0 skips empty space without retiring a ray): "
+                             "it is not an option of the plain render or of cull")
         culled = None
         if cull is not None:
             from . import cull as cull_mod
             train = torch.is_grad_enabled() and hasattr(self, "_store") and any(p.requires_grad for _, p, _, n, _ in self._store.entries if n > 0)
             culled = cull_mod.check_options(self, cull, slab, early_stop, train)
         elif early_stop is not None:
-            return self._run_early_stop(rays_o, rays_d, time, num_steps, perturb, early_stop, slab)
+            return self._run_early_stop(rays_o, rays_d, time, num_steps, perturb, early_stop, slab, occupancy)
         if not self.fused:  # four or sixteen channels per plane: sampling, density(), compositing, attribute() one after the other
             return LiDAR_Renderer.run(self, rays_o, rays_d, time, num_steps=num_steps, perturb=perturb, noise=noise)
         prefix = rays_o.shape[:-1]
@@ -192,17 +198,24 @@ class LiDAR4D(LiDAR_Renderer):
             **extra,
         }
 
-    def _run_early_stop(self, rays_o, rays_d, time, num_steps, perturb, early_stop, slab):
+    def _run_early_stop(self, rays_o, rays_d, time, num_steps, perturb, early_stop, slab, occupancy=None):
         from . import early_stop as es
         train = False
         if torch.is_grad_enabled() and hasattr(self, "_store"):
             train = any(p.requires_grad for _, p, _, n, _ in self._store.entries if n > 0)
         eps, S = es.check_options(self, early_stop, slab, perturb, train)
+        grid_kw = {}
+        if occupancy is not None:
+            from .occupancy import OccupancyGrid
+            if not isinstance(occupancy, OccupancyGrid):
+                raise ValueError(f"occupancy must be None or an OccupancyGrid (occupancy.py), got {occupancy!r}")
+            occupancy.check_call(self, time, num_steps)
+            grid_kw = {"occupancy": occupancy}
         prefix = rays_o.shape[:-1]
         rays_o = rays_o.contiguous().view(-1, 3).float()
         rays_d = rays_d.contiguous().view(-1, 3).float()
         depth, image, wsum, weights, z_vals, idx, count, evaluated, retired_at = es.run(
-            self, rays_o, rays_d, _t_device(time, rays_o.device), num_steps, eps, S)
+            self, rays_o, rays_d, _t_device(time, rays_o.device), num_steps, eps, S, **grid_kw)
         return {
             "depth_lidar": depth.view(*prefix),
             "image_lidar": image.view(*prefix, self.out_lidar_dim),

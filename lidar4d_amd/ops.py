@@ -304,15 +304,33 @@ def mlp_bwd(x16, act, dy16, weights16, n_hidden, grad_w, inv_loss_scale, n_rows=
 
 
 # ---- renderer --------------------------------------------------------------------------------------
-def sample_rays(rays_o, rays_d, lin, noise, near, far, bound, want_xyz=True):
+def sample_rays(rays_o, rays_d, lin, noise, near, far, bound, want_xyz=True, occ=None, slab=None):
+    """-> z_vals [N, T], xyz [N * T, 3] or None.  occ: ``(bits, R)`` -- the int32 words of an R^3 occupancy bit grid (occupancy.py) --
+    with ``slab``: -> z_vals, xyz, flags [N, ceil(T / slab)] uint8, 1 where a sample of that slab of the ray lies in a set cell."""
     _chk(rays_o, torch.float32, "rays_o"), _chk(rays_d, torch.float32, "rays_d"), _chk(lin, torch.float32, "lin")
     _chk(noise, torch.float32, "noise")
     N, T = rays_o.shape[0], lin.shape[0]
     z = torch.empty(N, T, dtype=torch.float32, device=rays_o.device)
     xyz = torch.empty(N * T, 3, dtype=torch.float32, device=rays_o.device) if want_xyz else None
+    if occ is None:
+        call("l4d_sample_rays", _p(rays_o), _p(rays_d), _p(lin), _p(noise), N, T, float(near), float(far), float(bound),
+             _p(z), _p(xyz), None, 0, 0, None, _stream())
+        return z, xyz
+    bits, R = occ
+    _chk(bits, torch.int32, "occ bits")
+    R = int(R)
+    if isinstance(slab, bool) or not isinstance(slab, int) or slab < 1:
+        raise ValueError(f"sample_rays: occ needs slab, a positive int, got {slab!r}")
+    if R < 1 or bits.numel() < (R ** 3 + 31) // 32:
+        raise ValueError("sample_rays: occ bits hold fewer than ceil(R^3 / 32) words")
+    if T < 1 or slab > 0x7fffffff:
+        raise ValueError("sample_rays: occ needs T >= 1 and slab < 2^31")
+    flags = torch.empty(N, -(-T // slab), dtype=torch.uint8, device=rays_o.device)
+    if N == 0:  # (an empty tensor has a null pointer, which the entry point refuses for slab_flags)
+        return z, xyz, flags
     call("l4d_sample_rays", _p(rays_o), _p(rays_d), _p(lin), _p(noise), N, T, float(near), float(far), float(bound),
-         _p(z), _p(xyz), _stream())
-    return z, xyz
+         _p(z), _p(xyz), _p(bits), R, slab, _p(flags), _stream())
+    return z, xyz, flags
 
 
 def sample_rays_xt(rays_o, rays_d, lin, noise, t_dev, near, far, bound, live=None, n_live=None, s0=0, S=None, out=None):

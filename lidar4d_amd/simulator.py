@@ -45,15 +45,17 @@ def _grey(img):
 class Simulator:
     def __init__(self, name, opt, model, device=None, mute=False, fp16=False, workspace="simulation",
                  use_checkpoint="latest_model", use_refine=True, H_lidar=66, W_lidar=1030, to_points=None, early_stop=None,
-                 slab=96):
+                 slab=96, occupancy=None):
         """opt: namespace with at least ``scale`` and ``fov_lidar`` (every attribute is also forwarded to
         ``model.render`` as keyword, like the reference does).  to_points(depth_m [H,W], intensity [H,W], fov) -> [n,4]
         defaults to the device kernel lidar4d_amd.convert.pano_to_lidar_with_intensities.  early_stop / slab: handed to
-        ``model.render`` when ``early_stop`` is not None (lidar4d_amd/early_stop.py: rays are retired once their transmittance is below it)."""
+        ``model.render`` when ``early_stop`` is not None (lidar4d_amd/early_stop.py: rays are retired once their transmittance is below it).
+        occupancy: None, or a dict of ``OccupancyGrid.build``'s keywords (needs early_stop): one grid is built per frame, at that
+        frame's time, and the march skips the slabs it calls empty (lidar4d_amd/occupancy.py)."""
         self.name, self.opt, self.mute, self.fp16 = name, opt, mute, fp16
         self.workspace, self.use_checkpoint, self.use_refine = workspace, use_checkpoint, use_refine
         self.H_lidar, self.W_lidar = H_lidar, W_lidar
-        self.early_stop, self.slab = early_stop, slab
+        self.early_stop, self.slab, self.occupancy = early_stop, slab, occupancy
         self.time_stamp = time.strftime("%Y-%m-%d_%H-%M-%S")
         self.device = device if device is not None else torch.device("cuda:0" if torch.cuda.is_available() else "cpu")
         self.model = model.to(self.device) if hasattr(model, "to") else model
@@ -104,6 +106,9 @@ class Simulator:
             opt_kw.update(early_stop=self.early_stop, slab=self.slab)
         pred_lidar = None
         for i in range(rays_o_lidar.shape[0]):
+            if self.occupancy is not None:
+                from .occupancy import for_frame
+                opt_kw.update(for_frame(self.model, times_lidar[i:i + 1], opt_kw.get("num_steps", 768), self.occupancy))
             out = self.model.render(rays_o_lidar[i:i + 1], rays_d_lidar[i:i + 1], times_lidar[i:i + 1], staged=True, perturb=False,
                                     **opt_kw)
             image = out["image_lidar"].reshape(-1, H, W, 2)

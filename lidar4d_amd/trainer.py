@@ -881,6 +881,14 @@ def _march_kw(early_stop, slab):
     return {} if early_stop is None else {"early_stop": early_stop, "slab": slab}
 
 
+def _grid_kw(trainer, time, occupancy):
+    """The render keyword of a frame's occupancy grid (occupancy.for_frame); none at all when ``occupancy`` is not set."""
+    if occupancy is None:
+        return {}
+    from .occupancy import for_frame
+    return for_frame(trainer.model, time, trainer.num_steps, occupancy)
+
+
 def _cull_kw(trainer):
     """The render keywords of a culled training step; none at all when ``cull`` is not set (the plain render's call)."""
     cull = getattr(trainer, "cull", None)
@@ -1214,10 +1222,11 @@ class Trainer:
             self.ema.update()
 
     @torch.no_grad()
-    def collect_refine_data(self, dataset=None, frames=None, max_ray_batch=4096, early_stop=None, slab=96):
+    def collect_refine_data(self, dataset=None, frames=None, max_ray_batch=4096, early_stop=None, slab=96, occupancy=None):
         """runner.py:824-863: render every frame of ``dataset`` (the reference's ``refine`` split: the training frames served
         whole; default: the trainer's own dataset) with the (frozen) field and stack what the U-Net sees --
-        returns (raydrop_input [B, 3, H, W], raydrop_gt [B, 1, H, W]) for ``refine_unet``.  early_stop / slab: ``test_step``'s."""
+        returns (raydrop_input [B, 3, H, W], raydrop_gt [B, 1, H, W]) for ``refine_unet``.  early_stop / slab / occupancy: ``test_step``'s
+        (the frame's grid is built from the EMA weights the render uses)."""
         dataset = self.dataset if dataset is None else dataset
         self.model.eval()
         if self.ema is not None:
@@ -1227,23 +1236,29 @@ class Trainer:
             fr = dataset.frame(k)
             H, W = fr["H_lidar"], fr["W_lidar"]
             out = self.model.render(fr["rays_o_lidar"], fr["rays_d_lidar"], fr["time"], staged=True, perturb=False,
-                                    max_ray_batch=max_ray_batch, num_steps=self.num_steps, **_march_kw(early_stop, slab))
+                                    max_ray_batch=max_ray_batch, num_steps=self.num_steps, **_march_kw(early_stop, slab),
+                                    **_grid_kw(self, fr["time"], occupancy))
             image = out["image_lidar"].reshape(-1, H, W, 2)
             inputs.append(torch.cat([image[..., 0], image[..., 1], out["depth_lidar"].reshape(-1, H, W)], dim=0).unsqueeze(0))
             gts.append(fr["images_lidar"][:, :, :, 0].unsqueeze(0))
         return torch.cat(inputs, 0).float().contiguous(), torch.cat(gts, 0).float().contiguous()
 
     @torch.no_grad()
-    def test_step(self, data, refine=True, perturb=False, max_ray_batch=4096, raydrop_loss="mse", alpha_r=0.01, early_stop=None, slab=96):
+    def test_step(self, data, refine=True, perturb=False, max_ray_batch=4096, raydrop_loss="mse", alpha_r=0.01, early_stop=None, slab=96,
+                  occupancy=None):
         """runner.py:438-470: render every ray of a frame in chunks (staged), refine the ray-drop probability with the
         U-Net on the stacked [ray-drop, intensity, depth] image, mask intensity and depth by ray-drop > 0.5.
         data: ``rays_o_lidar``/``rays_d_lidar`` [B, H*W, 3], ``time`` [B,1], ``H_lidar``, ``W_lidar``.
         Returns (pred_raydrop [1,H,W], pred_intensity [B,H,W], pred_depth [B,H,W]).
         early_stop (default None: every sample of every ray) / slab: handed to ``model.render`` -- rays are retired once their
-        transmittance is below ``early_stop``, tested every ``slab`` samples (lidar4d_amd/early_stop.py has the bound)."""
+        transmittance is below ``early_stop``, tested every ``slab`` samples (lidar4d_amd/early_stop.py has the bound).
+        occupancy (default None; needs early_stop): a dict of ``OccupancyGrid.build``'s keywords -- the frame's occupancy grid is built
+        here, at the frame's time and from the weights the model holds now, and the march skips the slabs it calls empty
+        (lidar4d_amd/occupancy.py: a heuristic; its audit measures what is skipped)."""
         H, W = data["H_lidar"], data["W_lidar"]
         out = self.model.render(data["rays_o_lidar"], data["rays_d_lidar"], data["time"], staged=True, perturb=perturb,
-                                max_ray_batch=max_ray_batch, num_steps=self.num_steps, **_march_kw(early_stop, slab))
+                                max_ray_batch=max_ray_batch, num_steps=self.num_steps, **_march_kw(early_stop, slab),
+                                **_grid_kw(self, data["time"], occupancy))
         image = out["image_lidar"].reshape(-1, H, W, 2)
         pred_raydrop, pred_intensity = image[..., 0], image[..., 1]
         pred_depth = out["depth_lidar"].reshape(-1, H, W)
@@ -1260,7 +1275,7 @@ class Trainer:
 
     @torch.no_grad()
     def evaluate(self, dataset=None, frames=None, refine=True, max_ray_batch=4096, raydrop_loss="mse", intensity_scale=1.0, raydrop_ratio=0.5,
-                 lpips_fn=None, early_stop=None, slab=96):
+                 lpips_fn=None, early_stop=None, slab=96, occupancy=None):
         """runner.py:379-434,553-682 without the PNG, progress-bar and tensorboard output: every frame (default: all) of
         ``dataset`` (default: the trainer's own; the reference evaluates its ``val`` split) is rendered on the EMA weights if there are any, scored by the evaluation loss of runner.py:418-422 (the
         trainer's criteria, the reference's default weights 1 / 0.01 / 0.1) and fed to the four meters of
@@ -1289,7 +1304,7 @@ class Trainer:
                 fr = dataset.frame(k)
                 pred_raydrop, pred_intensity, pred_depth = self.test_step(fr, refine=refine, max_ray_batch=max_ray_batch,
                                                                           raydrop_loss=raydrop_loss, alpha_r=0,  # unmasked
-                                                                          early_stop=early_stop, slab=slab)
+                                                                          early_stop=early_stop, slab=slab, occupancy=occupancy)
                 images = fr["images_lidar"].float()  # (fp16 ground truth widens exactly; the mask is 0 / 1)
                 gt_raydrop = images[:, :, :, 0]
                 gt_intensity = images[:, :, :, 1] * gt_raydrop
