@@ -22,7 +22,6 @@
 #include "wave_dev.h"
 #include "binscatter.h"
 #include <algorithm>
-#include <cstdlib>
 #include <type_traits>
 
 #define ST_GVS_MAX 0     // [0..8)  max |gvs| per plane scale
@@ -796,7 +795,8 @@ __global__ void __launch_bounds__(256) dynhash_expand_kernel(FieldDesc fd, Field
   const int lvl = blockIdx.y;
   const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= g.size[lvl]) return;
-  // (levels the LDS kernel walked by entry parity keep their part of Hbuf parity-major: [parity][entry >> 1])
+  // A level's part of Hbuf is parity-major, [parity][entry >> 1], exactly for the levels of parity_levels: the mask the task builder
+  // of l4d_density_encode_bwd fills while it hands those levels to dynhash_lds_kernel as parity tasks; entry-major for all others.
   const uint32_t hi = (parity_levels >> lvl) & 1u ? (i & 1u) * (g.size[lvl] >> 1) + (i >> 1) : i;
   const float h = Hbuf[hoff0 + g.offset[lvl] + hi] * pscale;
   if (h == 0.0f) return;
@@ -977,9 +977,10 @@ extern "C" int l4d_density_encode_bwd(const l4d_field_desc* f, const l4d_field_g
     // and every part streams all samples again.  Those levels get a launch of their own with 128 KB parts (one workgroup per CU,
     // half the passes: measured 1.51 -> 1.46 ms against 64 KB parts, gpurun_out/r4f); the levels that fit 64 KB keep two workgroups per CU.
     constexpr int big_kb = 128;
+    // parity_levels[p], bit l: level l of stack p is walked by entry parity, and its part of Hbuf is parity-major.  Set here and
+    // nowhere else, from the level's size and hashing alone, in the same branch that emits the parity tasks; dynhash_expand_kernel
+    // reads Hbuf by the same mask.
     uint32_t parity_levels[3] = {0u, 0u, 0u};
-    static int dh_parity = -1;  // (read once, like the library's other A/B switches)
-    if (dh_parity < 0) { const char* e = getenv("L4D_DH_PARITY"); dh_parity = (e && e[0] == '0') ? 0 : 1; }
     for (int group = 0; group < 2; ++group) {  // 0: levels that fit DYNHASH_LDS_KB; 1: larger ones
       const int lds_kb = group == 0 ? DYNHASH_LDS_KB : big_kb;
       const int max_entries = (lds_kb * 1024) / 8, fit = (DYNHASH_LDS_KB * 1024) / 8;
@@ -990,8 +991,8 @@ extern "C" int l4d_density_encode_bwd(const l4d_field_desc* f, const l4d_field_g
           const int size = (int)d.hd[p].size[l];
           if ((size <= fit) != (group == 0)) continue;
           // a hashed power-of-two level of exactly two windows: one task per entry PARITY (two corners per sample each) instead of
-          // one per index range (four each); L4D_DH_PARITY=0: the range form (A/B switch, tests/test_gpu_switches.py)
-          if (dh_parity && size == 2 * max_entries && is_pow2((uint32_t)size) && ((d.hd[p].hashed_mask >> l) & 1u)) {
+          // one per index range (four each); every other level takes the range form below
+          if (size == 2 * max_entries && is_pow2((uint32_t)size) && ((d.hd[p].hashed_mask >> l) & 1u)) {
             for (int par = 0; par < 2; ++par) {
               if (t.n >= MAX_TASKS) { l4d_set_error(1, "l4d_density_encode_bwd: too many hash tasks"); return 1; }
               t.plane[t.n] = p; t.lvl[t.n] = l; t.lo[t.n] = -1 - par; t.cnt[t.n] = size / 2;

@@ -85,7 +85,9 @@ struct SigmaOut {
   half_t* y;        // [P, 16]
   half_t* act;      // [P, 64] or null
   float* sigma;     // [P]
-  int persistent;   // 1: gridDim.x workgroups (one per CU) whose wavefronts each walk many 64-sample groups (see the kernel)
+  int persistent;   // 1 wherever SIGMA runs: gridDim.x workgroups (one per CU) whose wavefronts each walk many 64-sample groups (see the
+                    // kernel).  A run-time value on purpose: with SIGMA as the loop's compile-time condition the same body, at 253 of 256
+                    // VGPRs, is allocated with 164 bytes of scratch per lane (-Rpass-analysis=kernel-resource-usage, gfx950).
 };
 // -DENC_PHASE_CLOCK (tools/build_abl.sh, tools/phase_probe.py enc): cycles (s_memtime) a wavefront of the fused encode spends in every part of
 // a 64-sample group, sampled (wavefront 0 of every 8th workgroup); not compiled into the shipped library
@@ -734,23 +736,9 @@ extern "C" int64_t l4d_density_encode_fwd_workspace(const l4d_field_desc* f, int
   return enc_ws_hs_offset(f, P) + (hs_cols ? (int64_t)f->hash_static.n_levels * P * 8 : 0);
 }
 
-L4D_INTERNAL int l4d_hs_pairld();
 L4D_INTERNAL int l4d_hs_pair_ok(const GridDesc* g, int n_features, const void* table);
 L4D_INTERNAL int l4d_hashgrid_levels_launch(const GridDesc* g, int n_dims, int n_features, const float* x, int64_t P, int x_stride,
                                             const int* cols3, const void* table, void* lvlT, void* stream);
-// static grid through the level-major pre-pass (default; L4D_ENC_HS_SPLIT=0: gathered inside the encode kernel as in rounds 1-4)
-static int enc_hs_split() {
-  static int v = -1;
-  if (v < 0) { const char* e = getenv("L4D_ENC_HS_SPLIT"); v = (e && e[0] == '0') ? 0 : 1; }
-  return v;
-}
-
-// static grid's levels inside the LDS kernel's tasks (default; L4D_DH_HS_FUSED=0: the level-major pre-pass as a launch of its own, A/B)
-static int dh_hs_fused() {
-  static int v = -1;
-  if (v < 0) { const char* e = getenv("L4D_DH_HS_FUSED"); v = (e && e[0] == '0') ? 0 : 1; }
-  return v;
-}
 
 extern "C" int64_t l4d_plane_rows_workspace(const l4d_field_desc* f) {
   int64_t n = 0;
@@ -761,12 +749,6 @@ extern "C" int64_t l4d_plane_rows_workspace(const l4d_field_desc* f) {
 
 extern "C" int l4d_mlp_fwd_sigma(const void* x, int64_t P, int32_t in_pad, int32_t n_hidden, const void* weights, void* y, void* act,
                                  float* sigma, void* stream);
-// density network inside the encode kernel (default; L4D_ENC_SIGMA=0: a launch of its own behind it, A/B)
-static int enc_sigma_fused() {
-  static int v = -1;
-  if (v < 0) { const char* e = getenv("L4D_ENC_SIGMA"); v = (e && e[0] == '0') ? 0 : 1; }
-  return v;
-}
 // so: null, or where the density network's forward pass (n_hidden hidden layers) puts its outputs
 static int encode_fwd_impl(const l4d_field_desc* f, const float* xt, const void* flow16, const float* tinfo,
                            int64_t P, void* X, int32_t in_pad, void* hd_scratch, float* plane_rows, void* stream,
@@ -780,9 +762,9 @@ static int encode_fwd_impl(const l4d_field_desc* f, const float* xt, const void*
   }
   hipStream_t main_s = (hipStream_t)stream;
   // static grid: level-major pre-pass into the workspace (needs the workspace, the time-plane rows, F = 4 and enough points)
-  const bool hs_pre = hd_scratch && plane_rows && enc_hs_split() && f->hash_static.n_features == 4 && P >= ENC_HS_PRE_MIN_POINTS;
+  const bool hs_pre = hd_scratch && plane_rows && f->hash_static.n_features == 4 && P >= ENC_HS_PRE_MIN_POINTS;
   // ... inside the LDS kernel's tasks where the three grids pair up level by level, as a launch of its own behind it otherwise
-  const bool dh_hs = hs_pre && dh_hs_fused() && d.hs.n_levels == d.hd[1].n_levels && d.hs.n_levels == d.hd[2].n_levels;
+  const bool dh_hs = hs_pre && d.hs.n_levels == d.hd[1].n_levels && d.hs.n_levels == d.hd[2].n_levels;
   half_t* hsT = hs_pre ? (half_t*)((char*)hd_scratch + enc_ws_hs_offset(f, P)) : nullptr;
   if (hd_scratch) {
     if (d.hd[1].size[d.hd[1].n_levels - 1] > DH_MAX_ENTRIES || d.hd[2].size[d.hd[2].n_levels - 1] > DH_MAX_ENTRIES) {
@@ -823,7 +805,7 @@ static int encode_fwd_impl(const l4d_field_desc* f, const float* xt, const void*
              (const half_t*)flow16, tinfo, P, (const half_t*)hd_scratch, (half_t*)X, in_pad, pr, (const half_t*)nullptr, no_sigma)
   const SigmaOut no_sigma{nullptr, nullptr, nullptr, nullptr, 0};
   // the density network as the kernel's epilogue: the default network shape behind the level-major form of the encode
-  bool sigma_fused = so && hs_pre && in_pad == 128 && n_hidden == 1 && enc_sigma_fused();
+  bool sigma_fused = so && hs_pre && in_pad == 128 && n_hidden == 1;
   const int lds = ENC_SIGMA_FRAGS * 1024 + ENC_SIGMA_THREADS * (in_pad + 8) * 2;
   // (154 KB of dynamic LDS: a device that does not grant it takes the two-launch path below instead of failing at the launch)
   if (sigma_fused && hipFuncSetAttribute((const void*)density_encode_fwd_kernel<true, true, 0, 1, true>, hipFuncAttributeMaxDynamicSharedMemorySize, lds) != hipSuccess) {
@@ -831,18 +813,14 @@ static int encode_fwd_impl(const l4d_field_desc* f, const float* xt, const void*
     sigma_fused = false;
   }
   if (sigma_fused) {
-    static int persistent = -1, n_cu = 0;
-    if (persistent < 0) {
-      const char* e = getenv("L4D_ENC_PERSISTENT");
-      persistent = (e && e[0] == '0') ? 0 : 1;
+    static int n_cu = 0;
+    if (n_cu == 0) {
       int dev = 0;
       if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&n_cu, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || n_cu < 8) n_cu = 256;
     }
-    SigmaOut so_l = *so;
-    so_l.persistent = persistent;
-    const unsigned grid = persistent ? (unsigned)(n_cu / 8 * 8) : (unsigned)xcd_grid(ceil_div64(P, ENC_SIGMA_THREADS));  // one workgroup per CU (LDS)
-    L4D_LAUNCH((density_encode_fwd_kernel<true, true, 0, 1, true>), dim3(grid), dim3(ENC_SIGMA_THREADS), lds,
-               main_s, d, xt, (const half_t*)flow16, tinfo, P, (const half_t*)hd_scratch, (half_t*)X, in_pad, pr, (const half_t*)hsT, so_l);
+    // one workgroup per CU (LDS), a multiple of eight so that every XCD gets as many; their wavefronts walk the 64-sample groups
+    L4D_LAUNCH((density_encode_fwd_kernel<true, true, 0, 1, true>), dim3((unsigned)(n_cu / 8 * 8)), dim3(ENC_SIGMA_THREADS), lds,
+               main_s, d, xt, (const half_t*)flow16, tinfo, P, (const half_t*)hd_scratch, (half_t*)X, in_pad, pr, (const half_t*)hsT, *so);
   } else if (hs_pre) {
     L4D_LAUNCH((density_encode_fwd_kernel<true, true, 0, 1>), egrid, dim3(ENC_THREADS), enc_lds, main_s, d, xt,
                (const half_t*)flow16, tinfo, P, (const half_t*)hd_scratch, (half_t*)X, in_pad, pr, (const half_t*)hsT, no_sigma);
@@ -871,6 +849,6 @@ extern "C" int l4d_density_encode_sigma_fwd(const l4d_field_desc* f, const float
                                             int64_t P, void* X, int32_t in_pad, void* hd_scratch, float* plane_rows,
                                             const void* sigma_weights, int32_t n_hidden, void* y, void* act, float* sigma, void* stream) {
   if (!sigma_weights || !y || !sigma) { l4d_set_error(1, "l4d_density_encode_sigma_fwd: weights / y / sigma is null"); return 1; }
-  const SigmaOut so{(const half_t*)sigma_weights, (half_t*)y, (half_t*)act, sigma, 0};
+  const SigmaOut so{(const half_t*)sigma_weights, (half_t*)y, (half_t*)act, sigma, 1};
   return encode_fwd_impl(f, xt, flow16, tinfo, P, X, in_pad, hd_scratch, plane_rows, stream, &so, n_hidden);
 }

@@ -108,31 +108,18 @@ __device__ __forceinline__ void load_coords_nt(const float* __restrict__ x, int6
 // 128-byte LINE at whichever boundary it crosses: 264 G lane-loads/s chip-wide = the L2's 34 TB/s when the line is L2-resident,
 // 65 G/s = the fabric's 8.3 TB/s when it comes from the Infinity Cache -- for 4, 8 and 16 bytes per lane and for every cache
 // policy alike (tools/ubench/gather_policy.hip, profiles/r05_ubench_gather_policy.txt).  With all levels evaluated per sample
-// (the row kernels, the fused encode) every L2 sees all tables and the fine levels miss nearly always.  Two block orders:
-//   ORDER 0 (rounds 2-4): level l on the workgroups that land on XCD l % 8 (the dispatcher places block b on XCD b % 8): each L2
-//     holds ONE table, but the levels run side by side and a fine level then has ONE XCD's gather rate (33 G/s) for all its
-//     samples -- the launch lasts as long as the finest level on an eighth of the chip;
-//   ORDER 1 (round 5): the levels one after the other, chip-wide: the workgroups in flight at any moment (2,048 of 49,152 per
-//     level) all read the SAME table, every L2 holds a copy of it, and every level has the whole chip's gather rate.
+// (the row kernels, the fused encode) every L2 sees all tables and the fine levels miss nearly always.  Block order (ORDER 1):
+// the levels one after the other, chip-wide: the workgroups in flight at any moment (2,048 of 49,152 per level) all read the
+// SAME table, every L2 holds a copy of it, and every level has the whole chip's gather rate -- a level pinned to one XCD has
+// that XCD's rate (33 G/s) for all its samples, and the launch lasts as long as the finest level on an eighth of the chip.
 // The coordinate stream is read with non-temporal loads (it must not evict the table), results go out as coalesced 2F-byte
 // non-temporal stores.  (Placement is a performance assumption only: any block -> XCD map gives the same result.)
 template <int D, int F, bool PAIRLD = false>
 __global__ void __launch_bounds__(256) hashgrid_fwd_levels_kernel(GridDesc desc, const float* __restrict__ x, int64_t P, int x_stride,
                                                                  Cols cols, const half_t* __restrict__ table, int64_t n_tiles,
-                                                                 half_t* __restrict__ lvlT, int order) {
-  int lvl;
-  int64_t tile;
-  if (order == 0) {
-    const int xcd = blockIdx.x & 7;
-    const int64_t q = blockIdx.x >> 3;
-    const int li = (int)(q / n_tiles);
-    tile = q - (int64_t)li * n_tiles;
-    lvl = xcd + 8 * li;
-    if (lvl >= desc.n_levels) return;
-  } else {
-    lvl = (int)(blockIdx.x / n_tiles);
-    tile = blockIdx.x - (int64_t)lvl * n_tiles;
-  }
+                                                                 half_t* __restrict__ lvlT) {
+  const int lvl = (int)(blockIdx.x / n_tiles);
+  const int64_t tile = blockIdx.x - (int64_t)lvl * n_tiles;
   const int64_t p = tile * blockDim.x + threadIdx.x;
   if (p >= P) return;
   float xin[D];
@@ -147,25 +134,11 @@ __global__ void __launch_bounds__(256) hashgrid_fwd_levels_kernel(GridDesc desc,
   __builtin_nontemporal_store(*reinterpret_cast<V*>(h), reinterpret_cast<V*>(lvlT + ((int64_t)lvl * P + p) * F));
 }
 
-// block order of the level-major kernel: L4D_HG_ORDER=0 restores the XCD-pinned order of rounds 2-4 (A/B; default 1)
-static int hg_order() {
-  static int v = -1;
-  if (v < 0) { const char* e = getenv("L4D_HG_ORDER"); v = (e && e[0] == '0') ? 0 : 1; }
-  return v;
-}
-
-// x-neighbour pairs in one 16-byte load where aligned (hashgrid_dev.h PAIRLD; F = 4): L4D_HS_PAIRLD=0 switches it off (A/B)
-L4D_INTERNAL int l4d_hs_pairld() {
-  static int v = -1;
-  if (v < 0) { const char* e = getenv("L4D_HS_PAIRLD"); v = (e && e[0] == '0') ? 0 : 1; }
-  return v;
-}
-
-// The x-neighbour pair loads are legal where every pair is one aligned 16-byte load: F = 4, a 16-byte aligned table, and levels
-// that start on an even entry.  ONE predicate for both users (the level-major pre-pass below and the pair loads inside the
-// fused encode, fused.hip HSMODE 2: ADVICE r5).
+// The x-neighbour pair loads (hashgrid_dev.h PAIRLD) are legal where every pair is one aligned 16-byte load: F = 4, a 16-byte
+// aligned table, and levels that start on an even entry.  ONE predicate for both users (the level-major pre-pass below and the
+// pair loads inside the fused encode, fused.hip HSMODE 2: ADVICE r5).
 L4D_INTERNAL int l4d_hs_pair_ok(const GridDesc* g, int n_features, const void* table) {
-  bool ok = n_features == 4 && l4d_hs_pairld() && (reinterpret_cast<uintptr_t>(table) & 15) == 0;
+  bool ok = n_features == 4 && (reinterpret_cast<uintptr_t>(table) & 15) == 0;
   for (int l = 0; l < g->n_levels; ++l) ok = ok && (g->offset[l] & 1u) == 0;
   return ok ? 1 : 0;
 }
@@ -176,19 +149,18 @@ L4D_INTERNAL int l4d_hashgrid_levels_launch(const GridDesc* g, int n_dims, int n
   Cols c;
   for (int d = 0; d < 3; ++d) c.c[d] = d < n_dims ? cols3[d] : 0;
   const int64_t n_tiles = ceil_div64(P, 256);
-  const int order = hg_order();
-  const int64_t n_blocks = order == 0 ? n_tiles * ((g->n_levels + 7) / 8) * 8 : n_tiles * g->n_levels;
+  const int64_t n_blocks = n_tiles * g->n_levels;
   if (n_blocks > 0x7fffffffLL) { l4d_set_error(1, "hashgrid levels: too many workgroups"); return 1; }
   dim3 grid((unsigned)n_blocks), block(256);
 #define CALL(D, F)                                                                                                             \
   L4D_LAUNCH((hashgrid_fwd_levels_kernel<D, F>), grid, block, 0, (hipStream_t)stream, *g, x, P, x_stride, c, (const half_t*)table, \
-             n_tiles, (half_t*)lvlT, order);
+             n_tiles, (half_t*)lvlT);
   const bool pair_ok = l4d_hs_pair_ok(g, n_features, table) != 0;
   if (pair_ok) {
     if (n_dims == 2)
-      L4D_LAUNCH((hashgrid_fwd_levels_kernel<2, 4, true>), grid, block, 0, (hipStream_t)stream, *g, x, P, x_stride, c, (const half_t*)table, n_tiles, (half_t*)lvlT, order);
+      L4D_LAUNCH((hashgrid_fwd_levels_kernel<2, 4, true>), grid, block, 0, (hipStream_t)stream, *g, x, P, x_stride, c, (const half_t*)table, n_tiles, (half_t*)lvlT);
     else
-      L4D_LAUNCH((hashgrid_fwd_levels_kernel<3, 4, true>), grid, block, 0, (hipStream_t)stream, *g, x, P, x_stride, c, (const half_t*)table, n_tiles, (half_t*)lvlT, order);
+      L4D_LAUNCH((hashgrid_fwd_levels_kernel<3, 4, true>), grid, block, 0, (hipStream_t)stream, *g, x, P, x_stride, c, (const half_t*)table, n_tiles, (half_t*)lvlT);
   }
   else if (n_dims == 2 && n_features == 2) { CALL(2, 2) }
   else if (n_dims == 2 && n_features == 4) { CALL(2, 4) }
@@ -579,7 +551,7 @@ extern "C" int l4d_hashgrid_t_fwd(const l4d_grid_desc* desc, const float* x, int
   return 0;
 }
 
-// level-major form (default from 2^18 points on; L4D_FLOW_LEVELS=0: the row kernel, A/B)
+// level-major form (from 2^18 points on; the row kernel below that and for every shape the form does not cover)
 extern "C" int64_t l4d_hashgrid_t_fwd_workspace(const l4d_grid_desc* desc, int64_t P) {
   return HG_T_HEAD_BYTES + (int64_t)desc->n_levels * P * (desc->n_features / 4) * 2;  // time coefficients, then the level-major columns
 }
@@ -587,11 +559,9 @@ extern "C" int64_t l4d_hashgrid_t_fwd_workspace(const l4d_grid_desc* desc, int64
 extern "C" int l4d_hashgrid_t_fwd_ws(const l4d_grid_desc* desc, const float* x, int64_t P, int32_t x_stride,
                                      const int32_t* cols, const void* const* tables, int32_t n_slices, const float* t,
                                      void* out, int32_t out_stride, int32_t out_is_half, void* workspace, void* stream) {
-  static int enabled = -1;
-  if (enabled < 0) { const char* e = getenv("L4D_FLOW_LEVELS"); enabled = (e && e[0] == '0') ? 0 : 1; }
   const int FO = desc->n_features / 4, width = desc->n_levels * FO;
   const int64_t n_tiles = ceil_div64(P, 256);
-  if (!workspace || !enabled || !out_is_half || P < (1 << 18) || desc->n_features != 8 || desc->n_dims != 3 || width % 8 || out_stride % 8 ||
+  if (!workspace || !out_is_half || P < (1 << 18) || desc->n_features != 8 || desc->n_dims != 3 || width % 8 || out_stride % 8 ||
       ((uintptr_t)out & 15) || n_tiles * desc->n_levels > 0x7fffffffLL)
     return l4d_hashgrid_t_fwd(desc, x, P, x_stride, cols, tables, n_slices, t, out, out_stride, out_is_half, stream);
   if (check_t(desc, n_slices)) return 1;

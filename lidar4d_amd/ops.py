@@ -4,7 +4,6 @@ Every wrapper checks device / dtype / contiguity, allocates nothing it was not a
 on the current torch stream.  Tensors must live on a HIP device: there is no CPU fallback.
 """
 import ctypes as C
-import os
 
 import torch
 
@@ -276,9 +275,8 @@ def mlp_recompute_supported(in_pad, n_hidden, hidden=64):
         return False
     if in_pad == 128 and n_hidden == 1:
         # the density network (round 5): its forward runs as the encode kernel's epilogue and stores 128 B less per sample, the backward
-        # reads 128 B less and recomputes the hidden layer from the row it reads anyway: 32.08 -> 31.91 ms per step (gpurun_out/s6;
-        # L4D_MLP_RECOMP_SIGMA=0: store them, A/B)
-        return os.environ.get("L4D_MLP_RECOMP_SIGMA") != "0"
+        # reads 128 B less and recomputes the hidden layer from the row it reads anyway: 32.08 -> 31.91 ms per step
+        return True
     return in_pad <= 32 and 1 <= n_hidden <= 3
 
 

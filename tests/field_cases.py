@@ -67,9 +67,7 @@ lattice of hashgrid_cases.py; the ray clouds of the band-skip cases: multiples o
                                 d = sum_{s, k} [ 24 u |dv_k gv_k| + 8 u M |gv_k| ] * mult,  M = max |time plane value| of the scale,
                               then |got - ref| <= d + 2^-11 (|ref| + d) + 2^-25.
 
-ROUTES THAT NO ARGUMENT SELECTS (environment switches, read once per process; tests/test_gpu_switches.py): HSMODE 0 with
-L4D_ENC_HS_SPLIT / L4D_HS_PAIRLD = 0 on an aligned table, the non-persistent epilogue (L4D_ENC_PERSISTENT = 0), the level-major pre-pass
-as a launch of its own with EQUAL level counts (L4D_DH_HS_FUSED = 0), the range form of a two-window hashed level (L4D_DH_PARITY = 0).
+Every route the library launches is selected by its arguments, and the route map below (``fwd_routes``, ``bwd_routes``) is complete.
 
 Largest |error| / bound observed on an MI355X (printed by test_gpu_field_exact.py): OBSERVED below.  They are observations, not
 inputs to the bounds.

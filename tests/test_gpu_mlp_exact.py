@@ -83,9 +83,8 @@ def test_every_shape_equals_float64(in_pad, n_hidden, P):
         assert sigma.shape == (P,)
 
 
-def test_recompute_covers_the_documented_shapes(monkeypatch):
+def test_recompute_covers_the_documented_shapes():
     ops = ops_()
-    monkeypatch.delenv("L4D_MLP_RECOMP_SIGMA", raising=False)  # the A/B switch that stores the density network's activations
     got = {s for s in mx.SHAPES if ops.mlp_recompute_supported(*s)}
     assert got == {s for s in mx.SHAPES if s[0] <= 32} | {(128, 1)}
 

@@ -1,7 +1,5 @@
-"""Run-time A/B switches of the round-5 structural changes ("Round 5 added"): every non-default setting is a
-code path the default GPU suite never takes.  Each one renders and back-propagates the same batch in a fresh process (the library
-reads its switches once) and must reproduce the default build's outputs -- bit for bit in the forward pass (the variants differ in
-WHERE a lookup runs and in which order table lines are fetched, not in arithmetic), to fp32 summation order in the gradients."""
+"""The library's one run-time switch, L4D_TRACE (csrc/capi.cpp): a diagnostic that must not change what is computed.  The same batch
+is rendered and back-propagated in a fresh process with and without it (the library reads the switch once per process)."""
 import json
 import os
 import subprocess
@@ -55,19 +53,6 @@ def _run(env_extra, want_stderr=False):
 @pytest.fixture(scope="module")
 def default_digest():
     return _run({})
-
-
-@pytest.mark.parametrize("switch", ["L4D_ENC_HS_SPLIT=0", "L4D_HS_PAIRLD=0", "L4D_HG_ORDER=0", "L4D_FLOW_LEVELS=0", "L4D_ENC_SIGMA=0",
-                                    "L4D_ENC_PERSISTENT=0", "L4D_MLP_RECOMP_SIGMA=0", "L4D_DH_PARITY=0", "L4D_ENC_HS_SPLIT=0,L4D_HS_PAIRLD=0"])
-def test_switch_reproduces_the_default_path(switch, default_digest):
-    got = _run(dict(kv.split("=") for kv in switch.split(",")))
-    assert got["finite"] and default_digest["finite"]
-    for k in ("depth", "image", "weights"):
-        assert got[k] == default_digest[k], (switch, k)  # forward: bit-identical
-    for k in ("grad_abs_sum", "grad_max", "grad_proj"):  # backward: the same contributions; float atomics order the dW / plane flushes
-        a, b = got[k], default_digest[k]
-        assert abs(a - b) <= 2e-4 * max(abs(b), 1e-12) + (1e-6 * default_digest["grad_abs_sum"] if k == "grad_proj" else 0.0), (switch, k, a, b)
-
 
 
 def test_trace_switch_names_every_launch_and_changes_nothing(default_digest):

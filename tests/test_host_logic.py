@@ -557,3 +557,30 @@ def test_resolve_knobs_tool(tmp_path):
     assert "#define KEEP 64  // tile" in out and "#ifndef KEEP" not in out and "#define A" not in out and "#define B" not in out
     assert "#ifdef __HIPCC__" in out and "int dev;" in out and "not_gone" in out and "int gone;" not in out and "a2" not in out and out.rstrip().endswith("int tail;")
     assert out.count("#endif") == 1 and out.count("#if") == 1
+
+
+def test_shipped_code_reads_two_environment_variables():
+    """Which kernels run is decided by the arguments of a call.  The process environment reaches the shipped code in two places:
+    L4D_TRACE (csrc/capi.cpp, a diagnostic that changes no result) and L4D_LIB (_lib.py, the path of an ablation build).  Every
+    read names its variable as a string literal, so that this list is the whole list."""
+    import glob
+    csrc = glob.glob(os.path.join(ROOT, "lidar4d_amd", "csrc", "*"))
+    assert len(csrc) > 40
+    c_literal, c_reads = set(), 0
+    for path in csrc:
+        text = open(path, errors="replace").read()
+        c_reads += len(re.findall(r"\bgetenv\s*\(", text))
+        c_literal_here = re.findall(r"\bgetenv\s*\(\s*\"([^\"]*)\"", text)
+        c_literal |= set(c_literal_here)
+        c_reads -= len(c_literal_here)
+    assert c_literal == {"L4D_TRACE"} and c_reads == 0, (c_literal, c_reads)
+    py = glob.glob(os.path.join(ROOT, "lidar4d_amd", "*.py"))
+    assert len(py) > 30
+    py_literal, py_reads = set(), 0
+    for path in py:
+        text = open(path).read()
+        py_reads += len(re.findall(r"\benviron\b|\bgetenv\b", text))
+        here = re.findall(r"\bos\.environ(?:\.get\(|\[)\s*[\"']([^\"']*)[\"']|\bos\.getenv\(\s*[\"']([^\"']*)[\"']", text)
+        py_literal |= {a or b for a, b in here}
+        py_reads -= len(here)
+    assert py_literal == {"L4D_LIB"} and py_reads == 0, (py_literal, py_reads)

@@ -93,11 +93,10 @@ def test_mixed_width_model_has_the_oracles_state_dict(tmp_path):
         checkpoint.load_checkpoint(path, LiDAR4D(**SMALL_MODEL))
 
 
-def test_width_64_calls_what_it_called(monkeypatch):
+def test_width_64_calls_what_it_called():
     """ops.mlp_fwd / mlp_bwd / mlp_fwd_sigma with hidden = 64 (the default) go to liblidar4d_hip.so's entry points, other widths to
     liblidar4d_mlp.so's, and only the default width may skip storing its activations."""
     from lidar4d_amd import ops
-    monkeypatch.delenv("L4D_MLP_RECOMP_SIGMA", raising=False)
     assert ops.mlp_recompute_supported(16, 2) and ops.mlp_recompute_supported(128, 1, 64)
     assert not any(ops.mlp_recompute_supported(i, n, h) for h in mw.WIDTHS for i in mw.IN_PADS for n in (1, 2, 3))
     x = torch.zeros(4, 32, dtype=torch.float16)
