@@ -25,6 +25,10 @@ CASES = {
     "33x70_intensity": (33, 70, 1.0, 0.3, 0.1, 0),     # ragged tiles in both directions; the intensity bounds
     "66x1030": (66, 1030, 80.0, 0.3, 0.1, 0),          # the real frame: several tiles, histogram over several workgroups
     "66x1030_ties": (66, 1030, 80.0, 0.7, 0.0, 0),     # more than half the pixels have |d| = 0: mass ties, median exactly 0
+    # past the bounded grids of csrc/evalmeter.hip (EM_THREADS 256, EM_CHUNK 2048, EM_MAX_BLOCKS 1024), eight rows tall:
+    "8x65600": (8, 65600, 80.0, 0.3, 0.1, 0),          # 524,800 pixels = 257 partials: the `i += EM_THREADS` loops turn twice
+    "8x262160": (8, 262160, 80.0, 0.3, 0.1, 0),        # 2,097,280 pixels = 1025 chunks: errors / select kernels stride the grid
+    "8x262160_ties": (8, 262160, 80.0, 0.7, 0.0, 0),   # the same with mass ties: the selection's strided histogram
 }
 
 

@@ -2,7 +2,8 @@
 restatement of tests/meters_ref.py, DepthMeter / IntensityMeter on top of it, and Trainer.evaluate.
 
 Bounds.  Device and restatement clamp and subtract in fp32 identically and work in fp64 from there on, so they differ by the
-order of fp64 sums only: RMSE within 1e-10 relative (worst case N * 2^-53 = 8e-12 at 67,980 pixels), SSIM and PSNR within 1e-9
+order of fp64 sums only: RMSE within 1e-10 relative (worst case N * 2^-53 = 8e-12 at 67,980 pixels; max(1e-10, 4 N 2^-53) for the
+two sizes past the kernels' bounded grids, see _check_row), SSIM and PSNR within 1e-9
 absolute (two fp64 summation orders of the restatement differ by 1e-15).  The median is a selection, not a sum: bit-equal to
 np.median of the float32 |d|.  The mean over a meter's updates is one more fp64 sum of a few values: 4 ulp."""
 import functools
@@ -36,14 +37,20 @@ def _device_errors(pred, gt, lo, hi):
     return out.cpu().numpy()
 
 
-def _check_row(got, want, tag="", medae_ulp=0):
-    """[rmse, medae, ssim, psnr] under the module docstring's bounds; NaN must meet NaN."""
+def _check_row(got, want, tag="", medae_ulp=0, n_pix=0):
+    """[rmse, medae, ssim, psnr] under the module docstring's bounds; NaN must meet NaN.  The RMSE bound follows the worst case of
+    a sum of ``n_pix`` fp64 terms taken in another order, N * 2^-53 relative, and 1e-10 is that bound's round value at the real
+    frame's 67,980 pixels.  The worst case grows with N -- 5.8e-11 at 8 x 65,600 pixels and 2.3e-10 at 8 x 262,160, the two sizes
+    that make the kernels stride (tests/meters_ref.py), the second already past 1e-10 -- so the bound is
+    max(1e-10, 4 * N * 2^-53): 2.3e-10 and 9.3e-10 at those two, and 1e-10, unchanged, wherever N is below 225,000 pixels (every
+    earlier case, and every caller that passes no ``n_pix``)."""
+    rmse_tol = max(1e-10, 4 * n_pix * 2.0 ** -53)
     with np.errstate(invalid="ignore"):  # (inf - inf where both are +inf)
         print(f"{tag}: got {got!r} want {want!r} diff {np.abs(got - want)!r}")
     assert np.array_equal(np.isnan(got), np.isnan(want)), tag
     rmse, medae, ssim, psnr = got
     if not np.isnan(want[0]):
-        assert abs(rmse - want[0]) <= 1e-10 * abs(want[0]), tag
+        assert abs(rmse - want[0]) <= rmse_tol * abs(want[0]), tag
     if not np.isnan(want[1]):
         if medae_ulp:
             assert abs(medae - want[1]) <= medae_ulp * EPS64 * abs(want[1]), tag
@@ -67,11 +74,11 @@ def _check_meter(got, want, tag=""):
 def test_image_errors_vs_float64_restatement(name):
     pred, gt, hi, want = _case(name)
     got = _device_errors(pred, gt, ref.LO, hi)
-    _check_row(got, want, name)
+    _check_row(got, want, name, n_pix=pred.size)
     # the median against numpy directly, as float32 bits
     d = np.abs(ref.clamp32(gt, ref.LO, hi) - ref.clamp32(pred, ref.LO, hi))
     assert np.float32(got[1]).tobytes() == np.float32(np.median(d)).tobytes() and got[1] == float(np.float32(got[1]))
-    if name == "66x1030_ties":
+    if name.endswith("_ties"):
         assert got[1] == 0.0
 
 

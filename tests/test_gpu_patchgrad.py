@@ -108,6 +108,20 @@ def test_fused_term_vs_depth_grad_loss_other_shapes(name, config):
     _compare(f"{name} {config}", _case(name, sobel=sobel), (name, sobel, True), kw)
 
 
+@pytest.mark.parametrize("config", ["huber_all4", "cos", "huber_all4_sobel", "cos_sobel"])
+@pytest.mark.parametrize("name", list(pc.STRIDE_CASES))
+def test_fused_term_past_its_grid(name, config):
+    """pc.STRIDE_CASES: more groups than PG_MAX_BLOCKS workgroups, for patches of at most a wavefront (4101 x 8 x 8: 1026 groups of
+    four) and for large ones (1030 x 5 x 13: a group each), so that a workgroup sweeps a second group over the LDS images of its
+    first; 262,464 elements, past the 1024 x 256 that pg_scale_kernel covers in one turn; and 35-pixel patches, one to a
+    wavefront with idle lanes.  The same comparison and bound as every other shape."""
+    sobel = config.endswith("_sobel")
+    kw = dict(kind="cos") if config.startswith("cos") else dict(kind="huber", **TERMS["all4"])
+    n, px, py = pc.shape_of(name)
+    assert (n > 1024 * (1 if px * py > 64 else 4 * (64 // (px * py)))) == (name != "9x5x7")
+    _compare(f"{name} {config}", _case(name, sobel=sobel), (name, sobel, True), dict(kw, sobel_grad=sobel))
+
+
 # ---- 3. fp16 ground truth -----------------------------------------------------------------------------------------------------------
 @pytest.mark.parametrize("terms", ["main", "all4"])
 @pytest.mark.parametrize("kind", ["l1", "mse"])  # (the restatement's huber_loss refuses a half target)
@@ -127,7 +141,7 @@ def test_fp16_ground_truth_with_sobel_is_refused():
 
 # ---- 4. same bits -------------------------------------------------------------------------------------------------------------------
 @pytest.mark.parametrize("name,kw", [("300x2x8", dict(kind="huber", **TERMS["all4"])), ("3x8x16", dict(kind="cos", sobel_grad=True)),
-                                     ("8x3x3", dict(kind="cos"))])
+                                     ("8x3x3", dict(kind="cos")), ("4101x8x8", dict(kind="huber", **TERMS["all4"]))])
 def test_same_input_same_bits(name, kw):
     from lidar4d_amd.trainer import patch_depth_grad_loss
     c = _case(name, sobel=bool(kw.get("sobel_grad")))
