@@ -445,7 +445,7 @@ __global__ void __launch_bounds__(PL_THREADS) plane_mask_kernel(const float* __r
   const float x = pts[(int64_t)i * 3], y = pts[(int64_t)i * 3 + 1], z = pts[(int64_t)i * 3 + 2];
   bool near = false;
   for (int h = 0; h < n_planes; ++h) near = near || plane_near(coeffs + (int64_t)h * 4, x, y, z, threshold);
-  if (near) mask[i] = 1;
+  if (near) mask[i] |= 1;  // (the header's contract: the other bits of the byte are the caller's)
 }
 
 extern "C" int l4dp_plane_score(const float* points, int64_t n, const int32_t* triples, int32_t n_hyp, float y_gap, float threshold,
